@@ -8,22 +8,28 @@ states, shared dynamics parameters, outputs u [N,B], pre
 [N,4,B] and status written.  A "step" = one full batched re-plan (Optimization::Step for every
 problem).
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, a 2 s untimed pre-heat
+(`--preheat-seconds`), W warm-up steps, exactly K timed steps and the line.  `--full` adds everything else described below
+(the fp64 record, the clock leg, the variants, the CPU baseline and its parity checks, the multi-GPU diagnostics).
+`--dump-outputs DIR` writes the outputs of the last timed step as DIR/<name>.npy (`dump_outputs`): the inputs are seeded,
+so two builds can be compared output for output.
+
 `--gpus N` (BASELINE.json configs[3] at N = 8): one process per GPU.  Rank r solves problems
 shard_range(N * 262144, r, N) of ONE seeded global batch (weak scaling, no data-path collective) and
 the control sequences are gathered to rank 0 over RCCL.  When WORLD_SIZE is not in the environment
 (plain `python bench.py --gpus N`) this process starts the N ranks itself -- before anything touches
 the GPU -- and relays rank 0's line; under `python -m torch.distributed.run` it is one of the ranks.
 
-For N > 1 the line carries every rank's own time per step, its SQP-kernel time and the stand-alone gather
+For N > 1 (with --full) the line carries every rank's own time per step, its SQP-kernel time and the stand-alone gather
 (`distributed.per_rank`, `distributed.gather_ms`).  `--as-rank R --of W` solves exactly rank R's shard of the W-GPU
 global batch alone on this GPU (no process group; `--parity-lanes K` holds K sampled lanes of it to the oracle).
 The launcher counts GPUs in sysfs (never through the runtime), polls all ranks and ends the run with the first non-zero
 exit code.
 
-The line's `roofline.issue` / `roofline.clock_GHz_measured` come from a child process on a diagnostic build of the same
-kernels (two clock stamps per wave, tools/kernel_clock.py), outside the timed region.
+With --full, the line's `roofline.issue` / `roofline.clock_GHz_measured` come from a child process on a diagnostic build
+of the same kernels (two clock stamps per wave, tools/kernel_clock.py), outside the timed region.
 
-The same line also carries the record of the parity dtype (`fp64`: the reference computes in double
+With --full, the same line also carries the record of the parity dtype (`fp64`: the reference computes in double
 only, optimization/single_pendulum_dynamics.hpp:185): the same workload at the same batch in fp64,
 timed the same way, with its own roofline and its control sequences compared with the CPU oracle.
 
@@ -387,6 +393,26 @@ def timed_region(torch, dist, sharding, opt, x0, outs, gather, steps, warmup, de
     prof = opt.profile_read()
     opt.profile_enable(False)
     return elapsed, own, prof, out, state["slot"], n_pre
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs writes at most this much; a larger batch is written as a seeded sample of lanes
+DUMP_FIELDS = ("u", "predicted_states", "status", "iterations", "ls_evals", "final_cost", "final_eq_l1")
+
+
+def dump_outputs(torch, out, path):
+    """What the timed path's last step handed its caller (BatchOutputs), as <path>/<field>.npy in the step's float dtype
+    (the int32 fields converted exactly).  The problem index is the last axis of every field; a batch larger than
+    DUMP_BYTES allows is written as the same seeded, sorted sample of lanes in every run."""
+    B = int(out.u.shape[-1])
+    fdt = np.float32 if out.u.dtype == torch.float32 else np.float64
+    per_lane = sum(int(np.prod(getattr(out, f).shape[:-1])) for f in DUMP_FIELDS) * np.dtype(fdt).itemsize
+    k = min(B, DUMP_BYTES // per_lane)
+    lanes = np.arange(B) if k == B else np.sort(np.random.default_rng(SEED + 1).choice(B, k, replace=False))
+    idx = torch.as_tensor(lanes, device=out.u.device)
+    os.makedirs(path, exist_ok=True)
+    for f in DUMP_FIELDS:
+        a = getattr(out, f).index_select(-1, idx).cpu().numpy().astype(fdt)
+        np.save(os.path.join(path, f + ".npy"), a)
 
 
 def roofline_of(prof, dtype, B, iters, steps, rate_per_gpu, nx=4):
@@ -1084,10 +1110,12 @@ def run_rank(args):
 
     elapsed, own_s, prof, out, slot, n_pre = timed_region(torch, dist, sharding, opt, x0, outs, gather, args.steps, args.warmup,
                                                           dev, local_rank, distributed, preheat_s=args.preheat_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, out, args.dump_outputs)
 
     # the gather on its own: the same [N, B] block from every rank to rank 0, nothing else in flight
     gather_ms = None
-    if gather is not None:
+    if gather is not None and args.full:
         reps = 5
         gather.finish()
         torch.cuda.synchronize()
@@ -1102,7 +1130,7 @@ def run_rank(args):
     # per-rank diagnostics (one small all-gather, outside the timed region): each rank's own time per step, the
     # average launch time of its SQP kernel, and its view of the stand-alone gather
     per_rank = None
-    if distributed:
+    if distributed and args.full:
         fused = prof.get("fused_sqp_kernel", (0.0, 0))
         per_rank = sharding.all_ranks([own_s / args.steps * 1e3, fused[0] / max(fused[1], 1),
                                        gather_ms if gather_ms is not None else -1.0],
@@ -1136,26 +1164,30 @@ def run_rank(args):
         line["as_rank"] = {"rank": shard_rank, "of": shard_world, "columns_of_global_batch": [lo, hi],
                            "note": "value is this one GPU's rate on that shard; no process group, no gather"}
     if distributed:
-        own_ms = [r[0] for r in per_rank]
         line["distributed"] = {"world_size_seen": dist.get_world_size(), "backend": dist.get_backend(),
                                "spawned_by_bench": os.environ.get("CPMPC_BENCH_SPAWNED", "0") == "1",
                                "shard_of_rank0": [lo, hi], "gather_ms": gather_ms,
-                               "devices_visible": n_dev,
-                               "per_rank": {"ms_per_step_own": own_ms, "ms_per_step_own_min": min(own_ms),
-                                            "ms_per_step_own_max": max(own_ms),
-                                            "sqp_kernel_ms_per_launch": [r[1] for r in per_rank],
-                                            "gather_ms": [r[2] if r[2] >= 0 else None for r in per_rank],
-                                            "note": "own = W..K steps + gather on that rank up to its own synchronize, "
-                                                    "before the closing barrier; ms_per_step is the max over ranks "
-                                                    "including the barrier"}}
-    # everything below is secondary: a failure in one leg is recorded, never raised (the primary line must print)
-    try:
-        st = out.status.cpu().numpy()
-        line["status_histogram"] = {pkg.capi.TERM_NAMES[int(c)]: int((st == c).sum()) for c in np.unique(st)}
-        line["mean_merit_evals_per_iter"] = float(out.ls_evals.float().mean().item() / args.iters)
-    except Exception as exc:  # noqa: BLE001
-        line["status_histogram"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-    if gather is not None:
+                               "devices_visible": n_dev}
+    if per_rank is not None:
+        own_ms = [r[0] for r in per_rank]
+        line["distributed"]["per_rank"] = {"ms_per_step_own": own_ms, "ms_per_step_own_min": min(own_ms),
+                                           "ms_per_step_own_max": max(own_ms),
+                                           "sqp_kernel_ms_per_launch": [r[1] for r in per_rank],
+                                           "gather_ms": [r[2] if r[2] >= 0 else None for r in per_rank],
+                                           "note": "own = W..K steps + gather on that rank up to its own synchronize, "
+                                                   "before the closing barrier; ms_per_step is the max over ranks "
+                                                   "including the barrier"}
+    # everything below is secondary, asked for by --full (or --parity-lanes): a failure in one leg is recorded, never raised
+    # (the primary line must print)
+    st = None
+    if args.full:
+        try:
+            st = out.status.cpu().numpy()
+            line["status_histogram"] = {pkg.capi.TERM_NAMES[int(c)]: int((st == c).sum()) for c in np.unique(st)}
+            line["mean_merit_evals_per_iter"] = float(out.ls_evals.float().mean().item() / args.iters)
+        except Exception as exc:  # noqa: BLE001
+            line["status_histogram"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+    if gather is not None and args.full:
         try:
             # what rank 0 holds after the last step: the control sequences of all ranks, in global problem order
             full = gather.assembled(slot)
@@ -1178,12 +1210,12 @@ def run_rank(args):
             idx = np.unique(np.linspace(0, B - 1, args.parity_lanes).astype(np.int64))
             u_cpu, _, st_cpu, _, _ = orc.step_batch_cold(orc.default_opt_params(**over), DYN_UI, 0.0, x0_np[:, idx])
             u_g = out.u.double().cpu().numpy()[:, idx]
-            ps, _ = parity_stats(u_g, u_cpu, st[idx], st_cpu)
+            ps, _ = parity_stats(u_g, u_cpu, out.status.cpu().numpy()[idx], st_cpu)
             ps.update({"bar": 1e-5, "global_columns_first_last": [int(lo + idx[0]), int(lo + idx[-1])]})
             line["as_rank"]["parity"] = ps
         except Exception as exc:  # noqa: BLE001
             line["as_rank"]["parity"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-    if as_rank:   # the secondary legs belong to the headline run
+    if as_rank or not args.full:   # the secondary legs belong to --full's headline run
         args.no_fp64 = args.no_variants = args.no_cpu_baseline = args.no_clock = True
     if world == 1 and args.dtype == "f32" and not args.no_fp64:
         try:
@@ -1391,13 +1423,19 @@ def parse_args(argv=None):
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--preheat-seconds", type=float, default=2.0, help="untimed pre-heat of the same steps before the "
                     "warm-up (0 disables); the timed region stays exactly --steps after --warmup")
+    ap.add_argument("--full", action="store_true", help="after the headline also run what it does not need: the fp64 record, "
+                    "the clock leg, the variants, the CPU baseline with its parity checks and, for N > 1, the stand-alone "
+                    "gather, the per-rank table and the check of the gathered block; the --no-* options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (u, "
+                    "predicted_states, status, iterations, ls_evals, final_cost, final_eq_l1) as DIR/<name>.npy in the "
+                    "step's float dtype; rank 0's shard for N > 1; a batch too large for 48 MB as a fixed seeded sample of lanes")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--no-fp64", action="store_true", help="skip the fp64 record")
     ap.add_argument("--no-variants", action="store_true", help="skip the secondary measurements (SURVEY 8d)")
     ap.add_argument("--no-clock", action="store_true", help="skip the shader-clock / issue-ceiling leg")
-    ap.add_argument("--plain-sqp", action="store_true", help="also run tools/plain_sqp.py's soaks (the price of the solver "
-                    "specification's three additions, DESIGN.md section 4) into the detail record")
+    ap.add_argument("--plain-sqp", action="store_true", help="implies --full; also run tools/plain_sqp.py's soaks (the price "
+                    "of the solver specification's three additions, DESIGN.md section 4) into the detail record")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where rank 0 writes the full record "
                     "(variants, notes, per-rank tables); stdout carries only the compact line")
     ap.add_argument("--pipeline", choices=["auto", "split", "fused"], default="auto")
@@ -1406,7 +1444,11 @@ def parse_args(argv=None):
     ap.add_argument("--of", type=int, default=None)
     ap.add_argument("--parity-lanes", type=int, default=0, help="with --as-rank: compare this many sampled lanes of the "
                     "shard with the CPU oracle (fp64 bar 1e-5)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.plain_sqp   # the soaks run among the variants
+    return args
 
 
 def main():

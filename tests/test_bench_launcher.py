@@ -1,5 +1,6 @@
 """bench.py --gpus N starts N ranks itself when WORLD_SIZE is unset (the way the driver calls it), before anything
 touches the GPU; each rank takes its shard of the one global batch.  Driven here on CPU with gloo ranks."""
+import importlib
 import json
 import os
 import subprocess
@@ -107,6 +108,50 @@ def test_the_driver_command_does_not_run_the_soaks():
     """The 1 000-tick plain-SQP soaks (four child processes) run only behind --plain-sqp."""
     assert bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).plain_sqp is False
     assert bench.parse_args(["--plain-sqp"]).plain_sqp is True
+
+
+def test_plain_run_leaves_the_secondary_legs_to_full():
+    """The driver's command runs the headline only; --full (or --plain-sqp, which runs among the variants) adds the rest."""
+    assert bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    assert bench.parse_args(["--full"]).full is True and bench.parse_args(["--plain-sqp"]).full is True
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_every_field_within_the_budget(tmp_path):
+    """--dump-outputs: every field of the step's outputs as <name>.npy in the step's float dtype, lanes on the last axis;
+    a batch over the byte budget as the same seeded sample of lanes in every run."""
+    torch = pytest.importorskip("torch")
+    N, nx = 40, 4
+
+    def outputs(B, dtype):
+        o = importlib.import_module("cart-pole-mpc_amd.batch").BatchOutputs()
+        lane = torch.arange(B, dtype=dtype)
+        o.u = lane.repeat(N, 1)
+        o.predicted_states = lane.repeat(N, nx, 1)
+        o.status, o.iterations, o.ls_evals = (torch.full((B,), v, dtype=torch.int32) for v in (3, 5, 7))
+        o.final_cost, o.final_eq_l1 = lane.clone(), -lane
+        return o
+
+    small = outputs(1000, torch.float64)
+    bench.dump_outputs(torch, small, str(tmp_path / "small"))
+    got = {f: np.load(str(tmp_path / "small" / (f + ".npy"))) for f in bench.DUMP_FIELDS}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["u"].shape == (N, 1000) and got["predicted_states"].shape == (N, nx, 1000)
+    assert np.array_equal(got["u"][7], np.arange(1000)) and np.array_equal(got["final_eq_l1"], -np.arange(1000))
+    assert np.all(got["status"] == 3) and np.all(got["ls_evals"] == 7)
+
+    big = outputs(262144, torch.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(torch, big, str(tmp_path / run))
+    files = [tmp_path / run / (f + ".npy") for run in ("a", "b") for f in bench.DUMP_FIELDS]
+    assert sum(os.path.getsize(str(p)) for p in files[:len(bench.DUMP_FIELDS)]) <= 64 << 20
+    ua, ub = np.load(str(tmp_path / "a" / "u.npy")), np.load(str(tmp_path / "b" / "u.npy"))
+    assert ua.dtype == np.float32 and 1000 < ua.shape[1] < 262144 and np.array_equal(ua, ub)
+    lanes = ua[0].astype(np.int64)
+    assert np.all(np.diff(lanes) > 0) and np.array_equal(np.load(str(tmp_path / "a" / "final_cost.npy")), ua[0])
 
 
 def test_global_batch_is_one_seeded_batch():

@@ -19,7 +19,7 @@ def test_bench_gpus_2_spawns_two_ranks_on_the_gpu(tmp_path):
     env["CPMPC_BENCH_SHARE_DEVICE"] = "1"
     detail = str(tmp_path / "bench_detail.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8192", "--steps", "3",
-                        "--warmup", "1", "--detail", detail], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--detail", detail], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     # stdout: the launcher relays rank 0's compact line and nothing else that looks like JSON
     json_lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

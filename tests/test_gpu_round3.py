@@ -48,7 +48,7 @@ def test_rccl_branch_in_a_world_of_one():
     """The code a rank of `bench.py --gpus 8` runs -- nccl process group on its device, ResultGather on device
     tensors, barrier, max-reduce of the time, per-rank all-gather -- executed in a world of one
     (CPMPC_BENCH_FORCE_DIST=1), so that RCCL code does not run for the first time in the driver's scaling run."""
-    line = _bench(["--gpus", "1", "--batch", "8192", "--steps", "3", "--warmup", "1", "--no-fp64", "--no-variants",
+    line = _bench(["--gpus", "1", "--batch", "8192", "--steps", "3", "--warmup", "1", "--full", "--no-fp64", "--no-variants",
                    "--no-cpu-baseline", "--no-clock"], {"CPMPC_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29533"})
     d = line["distributed"]
     assert d["backend"] == "nccl" and d["world_size_seen"] == 1
@@ -65,7 +65,8 @@ def test_rank_7_of_8_solves_its_full_shard_of_configs3():
     """BASELINE configs[3] is 2 097 152 problems over 8 GPUs: rank 7's share is columns 1 835 008 .. 2 097 151 of the one
     seeded global batch.  `bench.py --as-rank 7 --of 8` solves exactly that shard at full per-GPU size on this GPU (no
     process group), in the parity dtype, and 512 lanes sampled across it are held to the oracle."""
-    line = _bench(["--as-rank", "7", "--of", "8", "--dtype", "f64", "--steps", "2", "--warmup", "1", "--parity-lanes", "512"])
+    line = _bench(["--as-rank", "7", "--of", "8", "--dtype", "f64", "--steps", "2", "--warmup", "1", "--parity-lanes", "512",
+                   "--full"])
     a = line["as_rank"]
     assert a["rank"] == 7 and a["of"] == 8 and a["columns_of_global_batch"] == [1835008, 2097152]
     assert line["config"]["global_batch"] == 2097152 and line["config"]["batch_per_gpu"] == 262144
@@ -75,6 +76,27 @@ def test_rank_7_of_8_solves_its_full_shard_of_configs3():
     assert p["lanes"] >= 500 and p["lanes_over_1e-5"] == 0 and p["status_agree"] == p["lanes"], p
     assert p["global_columns_first_last"] == [1835008, 2097151]
     assert line["n_gpus"] == 1 and line["value"] > 1e6
+
+
+def test_plain_run_is_the_headline_and_dumps_what_the_timed_path_returned(pkg, tmp_path):
+    """The driver's command without --full runs none of the secondary legs.  --dump-outputs writes the last timed step's
+    outputs: bitwise what one cold step of a fresh handle returns for the benchmark's seeded states."""
+    import bench
+    B = 8192
+    d = str(tmp_path / "dump")
+    line = _bench(["--gpus", "1", "--batch", str(B), "--dtype", "f64", "--steps", "3", "--warmup", "1",
+                   "--preheat-seconds", "0", "--dump-outputs", d])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    for k in ("fp64", "variants", "cpu_baseline", "parity_sample", "parity_f64", "status_histogram", "distributed"):
+        assert k not in line, k
+    assert "issue" not in line["roofline"]
+    got = {f: np.load(os.path.join(d, f + ".npy")) for f in bench.DUMP_FIELDS}
+    opt = pkg.BatchOptimization(pkg.default_params(**NO_TOL), max_batch=B, dtype=torch.float64, device=0)
+    o = opt.step(T(bench.synth_states(bench.SEED, B)), DYN_UI, 0.0, want_predicted=True, want_stats=True)
+    for f in bench.DUMP_FIELDS:
+        want = getattr(o, f).cpu().numpy().astype(np.float64)
+        assert got[f].dtype == np.float64 and np.array_equal(got[f], want), f
+    opt.close()
 
 
 def test_shards_of_one_global_batch_do_not_depend_on_the_world_size(pkg):

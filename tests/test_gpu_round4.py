@@ -540,7 +540,7 @@ def test_bench_with_four_ranks_on_the_one_gpu(tmp_path):
     env["CPMPC_BENCH_SHARE_DEVICE"] = "1"
     detail = str(tmp_path / "bench_detail.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "4096", "--steps", "3",
-                        "--warmup", "1", "--detail", detail], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--detail", detail], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     last = r.stdout.strip().splitlines()[-1]
     compact = json.loads(last)

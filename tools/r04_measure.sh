@@ -14,7 +14,7 @@ O=gpurun_out/r04m
 mkdir -p $O
 case $PART in
 A)
-  python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+  python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
   ./tools/prof.sh r04 > $O/prof_f32.log 2>&1; echo "prof f32 rc=$?"
   ./tools/prof.sh r04_f64 --dtype f64 > $O/prof_f64.log 2>&1; echo "prof f64 rc=$?"
   ./tools/prof_workload.sh r04_per_problem_f32 per_problem > $O/prof_pp32.log 2>&1; echo "prof pp f32 rc=$?"
@@ -36,13 +36,13 @@ B)
   ;;
 C)
   for r in 0 1 2 3 4 5 6 7; do
-    python bench.py --as-rank $r --of 8 --dtype f64 --steps 3 --warmup 1 --parity-lanes 512 > $O/shard_$r.json 2> $O/shard_$r.err; echo "shard $r rc=$?"
+    python bench.py --full --as-rank $r --of 8 --dtype f64 --steps 3 --warmup 1 --parity-lanes 512 > $O/shard_$r.json 2> $O/shard_$r.err; echo "shard $r rc=$?"
   done
   ;;
 D)
   python tools/parity_sweep.py $O/parity_sweep.json > $O/parity_sweep.log 2>&1; echo "parity sweep rc=$?"
   ;;
 E)
-  python bench.py > $O/bench_box_${2:-x}.json 2> $O/bench_box_${2:-x}.err; echo "bench rc=$?"
+  python bench.py --full > $O/bench_box_${2:-x}.json 2> $O/bench_box_${2:-x}.err; echo "bench rc=$?"
   ;;
 esac

@@ -13,8 +13,8 @@ O=gpurun_out/r06m
 mkdir -p $O
 case $PART in
 S)
-  python bench.py --gpus 1 --steps 20 --warmup 5 --detail $O/bench_detail_20_${2:-x}.json > $O/bench_20_${2:-x}.json 2> $O/bench_20_${2:-x}.err; echo "bench 20 rc=$?"
-  python bench.py --gpus 1 --steps 200 --warmup 5 --no-variants --no-cpu-baseline --no-clock --detail $O/bench_detail_200_${2:-x}.json > $O/bench_200_${2:-x}.json 2> $O/bench_200_${2:-x}.err; echo "bench 200 rc=$?"
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail $O/bench_detail_20_${2:-x}.json > $O/bench_20_${2:-x}.json 2> $O/bench_20_${2:-x}.err; echo "bench 20 rc=$?"
+  python bench.py --full --gpus 1 --steps 200 --warmup 5 --no-variants --no-cpu-baseline --no-clock --detail $O/bench_detail_200_${2:-x}.json > $O/bench_200_${2:-x}.json 2> $O/bench_200_${2:-x}.err; echo "bench 200 rc=$?"
   ;;
 D)
   ./tools/prof_workload.sh r06_double_f32 double --dtype f32 > $O/prof_d32.log 2>&1; echo "prof double f32 rc=$?"
