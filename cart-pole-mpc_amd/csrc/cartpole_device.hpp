@@ -18,53 +18,17 @@ namespace cpmpc {
 template <typename R>
 struct Math;
 
-#ifndef CPMPC_F32_LIBM
-#define CPMPC_F32_LIBM 0  // 1: ocml sincosf/tanhf/sqrtf and IEEE division in the fp32 kernels
-#endif
-#ifndef CPMPC_F32_NATIVE_TRIG
-// 1 (default): v_sin_f32 / v_cos_f32.  Measured on MI355X: +13 % re-plans/s over the
-// polynomial below, and the fp32-vs-fp64 control error and the closed-loop balancing accuracy are the same
-// with either (fp32 rounding of the rest of the pipeline dominates).  0 selects the ~1-ulp polynomial.
-#define CPMPC_F32_NATIVE_TRIG 1
-#endif
-
 // fp32: the reference is fp64-only, so the fp32 kernels are free to use bounded-range routines.
 // Angles reaching sincos are at most a few turns (theta is wrapped to (-pi, pi] at every shooting node
-// and RK4 stages move it by < 1 rad), where a 3-term Cody-Waite reduction by pi/2 and degree-7/8
-// minimax polynomials are accurate to ~1 ulp; tanh uses the hardware exp2; sqrt and reciprocal use the
-// 1-ulp hardware instructions.
+// and RK4 stages move it by < 1 rad); tanh uses the hardware exp2; sqrt and reciprocal use the 1-ulp
+// hardware instructions.
 template <>
 struct Math<float> {
-#if CPMPC_F32_LIBM
-  static __device__ __forceinline__ void sincos(float x, float& s, float& c) { ::sincosf(x, &s, &c); }
-  static __device__ __forceinline__ float tanh(float x) { return ::tanhf(x); }
-  static __device__ __forceinline__ float tanh_scaled(float x, float scale, float) { return ::tanhf(x * scale); }
-  static __device__ __forceinline__ float sqrt(float x) { return ::sqrtf(x); }
-  static __device__ __forceinline__ float rcp(float x) { return 1.0f / x; }
-#else
+  // v_sin_f32 / v_cos_f32 on x/(2 pi).  Measured on MI355X: +13 % re-plans/s over a ~1-ulp Cody-Waite polynomial, with the
+  // same fp32-vs-fp64 control error and closed-loop balancing accuracy (fp32 rounding of the rest of the pipeline dominates).
   static __device__ __forceinline__ void sincos(float x, float& s, float& c) {
-#if CPMPC_F32_NATIVE_TRIG
-    s = __sinf(x);  // v_sin_f32 / v_cos_f32 on x/(2 pi); arguments here are at most a few turns
+    s = __sinf(x);
     c = __cosf(x);
-    return;
-#endif
-    const float kf = ::rintf(x * 0.63661977236758134f);  // nearest multiple of pi/2
-    float r = ::fmaf(-kf, 1.5703125f, x);                // pi/2 split in three (Cody-Waite)
-    r = ::fmaf(-kf, 4.837512969970703125e-4f, r);
-    r = ::fmaf(-kf, 7.54978995489188e-8f, r);
-    const int q = (int)kf;
-    const float r2 = r * r;
-    float sp = ::fmaf(r2, -1.9515295891e-4f, 8.3321608736e-3f);
-    sp = ::fmaf(sp, r2, -1.6666654611e-1f);
-    sp = ::fmaf(sp * r2, r, r);
-    float cp = ::fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f);
-    cp = ::fmaf(cp, r2, 4.166664568298827e-2f);
-    cp = ::fmaf(cp * r2, r2, ::fmaf(r2, -0.5f, 1.0f));
-    const bool swap = q & 1;
-    const float ss = swap ? cp : sp;
-    const float cc = swap ? sp : cp;
-    s = (q & 2) ? -ss : ss;
-    c = ((q + 1) & 2) ? -cc : cc;
   }
   static __device__ __forceinline__ float tanh(float x) {
     const float t = __expf(-2.0f * ::fabsf(x));  // in (0, 1]
@@ -79,7 +43,6 @@ struct Math<float> {
   }
   static __device__ __forceinline__ float sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
   static __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-#endif
   static constexpr bool kIncrementalTrig = false;  // v_sin_f32 / v_cos_f32 are cheaper than a rotation
   static constexpr bool kMergedReciprocals = false;
   static __device__ __forceinline__ float div(float a, float b) { return a / b; }
@@ -97,45 +60,28 @@ struct Math<float> {
 
 // fp64: the parity dtype.  The inlined library sincos / tanh cost 155 / 165 instructions per call (an RK4 step
 // without Jacobians 1 470, against ~45 per stage of actual dynamics), so fp64 gets its own routines, accurate to
-// about one ulp on the ranges this path produces (-DCPMPC_F64_LIBM=1 restores the library calls for A/B):
+// about one ulp on the ranges this path produces:
 //   sincos  Cody-Waite reduction by pi/2 in three 33-bit pieces (exact products for |x| < 2^20 * pi/2; pole angles
 //           are wrapped to (-pi, pi] at every node) + the classic degree-13 / degree-14 minimax kernels on
 //           [-pi/4, pi/4]; beyond that range a finite argument gives (0, 1) and a non-finite one NaN
 //   tanh    -t / (t + 2) with t = expm1(-2|x|): n = rint(y / ln 2), r = y - n ln 2 (hi/lo), degree-13 Taylor
 //           kernel on |r| <= ln2/2, t = 2^n p + (2^n - 1); exact odd symmetry, full relative accuracy at small |x|
-#ifndef CPMPC_F64_LIBM
-#define CPMPC_F64_LIBM 0
-#endif
 // Horner step p*z + C with the coefficient C read straight from a scalar register pair (VOP3 v_fma_f64 takes one
 // SGPR source).  Left to itself hipcc 7.2 keeps the ~24 fp64 polynomial coefficients of sincos/tanh in VGPRs across
 // the RK4 loops and, the kernel being at its register limit, re-assembles each one into an aligned VGPR pair
 // (v_mov_b64 + v_mov_b32) in front of a two-address v_fmac_f64: about 30 of the ~160 vector instructions of a stage
 // were such copies.  Materialising a coefficient in SGPRs is scalar-unit work that issues beside the vector stream.
-#ifndef CPMPC_F64_SGPR_COEF
-#define CPMPC_F64_SGPR_COEF 1
-#endif
 __device__ __forceinline__ double horner(double p, double z, double c) {
-#if CPMPC_F64_SGPR_COEF
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(z), "s"(c));
   return r;
-#else
-  return ::fma(p, z, c);
-#endif
 }
 
-#ifndef CPMPC_F64_IEEE_DIV
-#define CPMPC_F64_IEEE_DIV 0  // 1: compiler-expanded IEEE division and sqrt in the fp64 kernels (A/B of the Newton routines)
-#endif
 // The fp64 polynomial coefficients, read from constant memory instead of being immediates: as immediates every use costs
 // two s_mov_b32 in front of the v_fma_f64 that takes the pair (the kernel has no scalar registers to keep ~35 pairs
 // resident), and at ONE wave per SIMD -- where the fp64 fused kernel runs -- a scalar instruction takes an issue slot of
 // the wave like a vector one does (measured: 163 k instructions per wave x 4.75 cycles = the wave's residence time).
-// A scalar load brings up to eight coefficients in one instruction.  -DCPMPC_F64_COEF_TABLE=0 restores the immediates.
-#ifndef CPMPC_F64_COEF_TABLE
-#define CPMPC_F64_COEF_TABLE 1
-#endif
-#if CPMPC_F64_COEF_TABLE
+// A scalar load brings up to eight coefficients in one instruction.
 __constant__ double kCoef64[23] = {  // [0..7] sincos, [8..18] expm1 (tanh), [19..22] the rotation's own (it shares 12, 15, 16)
     2.75573137070700676789e-06,
     -1.98412698298579493134e-04,
@@ -164,16 +110,8 @@ __constant__ double kCoef64[23] = {  // [0..7] sincos, [8..18] expm1 (tanh), [19
 // (Reading the table through a pointer made opaque at the top of each routine, so that the loads stay inside the RK4
 // loops instead of being hoisted, spilled and read back with v_readlane, was tried: 27 scalar loads and 17 waits per step
 // replace 18 v_readlane and 22 s_mov -- no gain.)
-#define CPMPC_C64(I, LITERAL) (kCoef64[I])
-#else
-#define CPMPC_C64(I, LITERAL) (LITERAL)
-#endif
 template <>
 struct Math<double> {
-#if CPMPC_F64_LIBM
-  static __device__ __forceinline__ void sincos(double x, double& s, double& c) { ::sincos(x, &s, &c); }
-  static __device__ __forceinline__ double tanh(double x) { return ::tanh(x); }
-#else
   static __device__ __forceinline__ void sincos(double x, double& s, double& c) {
     const double kf = ::rint(x * 6.36619772367581382433e-01);  // nearest multiple of pi/2
     double r = ::fma(-kf, 1.57079632673412561417e+00, x);      // pi/2 = P1 + P2 + P3 (+ 8.5e-32)
@@ -182,17 +120,17 @@ struct Math<double> {
     const double z = r * r;
     // sin(r) = r + r z S(z)
     double sp = ::fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-    sp = horner(sp, z, CPMPC_C64(0, 2.75573137070700676789e-06));
-    sp = horner(sp, z, CPMPC_C64(1, -1.98412698298579493134e-04));
-    sp = horner(sp, z, CPMPC_C64(2, 8.33333333332248946124e-03));
-    sp = horner(sp, z, CPMPC_C64(3, -1.66666666666666324348e-01));
+    sp = horner(sp, z, kCoef64[0]);
+    sp = horner(sp, z, kCoef64[1]);
+    sp = horner(sp, z, kCoef64[2]);
+    sp = horner(sp, z, kCoef64[3]);
     const double sr = ::fma(r * z, sp, r);
     // cos(r) = w + ((1 - w) - z/2 + z z C(z)),  w = 1 - z/2
     double cp = ::fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-    cp = horner(cp, z, CPMPC_C64(4, -2.75573143513906633035e-07));
-    cp = horner(cp, z, CPMPC_C64(5, 2.48015872894767294178e-05));
-    cp = horner(cp, z, CPMPC_C64(6, -1.38888888888741095749e-03));
-    cp = horner(cp, z, CPMPC_C64(7, 4.16666666666666019037e-02));
+    cp = horner(cp, z, kCoef64[4]);
+    cp = horner(cp, z, kCoef64[5]);
+    cp = horner(cp, z, kCoef64[6]);
+    cp = horner(cp, z, kCoef64[7]);
     const double hz = 0.5 * z;
     const double w = 1.0 - hz;
     const double cr = w + (((1.0 - w) - hz) + z * z * cp);
@@ -217,17 +155,17 @@ struct Math<double> {
     r = ::fma(-nf, 1.90821492927058770002e-10, r);
     // expm1(r) = r + r^2 (1/2! + r (1/3! + ... + r / 13!)),  |r| <= ln2 / 2
     double p = 1.6059043836821613e-10;                       // 1/13!
-    p = horner(p, r, CPMPC_C64(8, 2.08767569878680989792e-09));            // 1/12!
-    p = horner(p, r, CPMPC_C64(9, 2.50521083854417187751e-08));            // 1/11!
-    p = horner(p, r, CPMPC_C64(10, 2.75573192239858906526e-07));            // 1/10!
-    p = horner(p, r, CPMPC_C64(11, 2.75573192239858906526e-06));            // 1/9!
-    p = horner(p, r, CPMPC_C64(12, 2.48015873015873015873e-05));            // 1/8!
-    p = horner(p, r, CPMPC_C64(13, 1.98412698412698412698e-04));            // 1/7!
-    p = horner(p, r, CPMPC_C64(14, 1.38888888888888888889e-03));            // 1/6!
-    p = horner(p, r, CPMPC_C64(15, 8.33333333333333333333e-03));            // 1/5!
-    p = horner(p, r, CPMPC_C64(16, 4.16666666666666666667e-02));            // 1/4!
-    p = horner(p, r, CPMPC_C64(17, 1.66666666666666666667e-01));            // 1/3!
-    p = horner(p, r, CPMPC_C64(18, 0.5));                                   // 1/2!
+    p = horner(p, r, kCoef64[8]);  // 1/12!
+    p = horner(p, r, kCoef64[9]);  // 1/11!
+    p = horner(p, r, kCoef64[10]);  // 1/10!
+    p = horner(p, r, kCoef64[11]);  // 1/9!
+    p = horner(p, r, kCoef64[12]);  // 1/8!
+    p = horner(p, r, kCoef64[13]);  // 1/7!
+    p = horner(p, r, kCoef64[14]);  // 1/6!
+    p = horner(p, r, kCoef64[15]);  // 1/5!
+    p = horner(p, r, kCoef64[16]);  // 1/4!
+    p = horner(p, r, kCoef64[17]);  // 1/3!
+    p = horner(p, r, kCoef64[18]);  // 1/2!
     p = ::fma(r * r, p, r);
     const double two_n = ::ldexp(1.0, (int)nf);              // n in [-116, 0]
     const double t = ::fma(two_n, p, two_n - 1.0);           // expm1(y) in (-1, 0]
@@ -244,17 +182,17 @@ struct Math<double> {
     double r = ::fma(-nf, 6.93147180369123816490e-01, y);
     r = ::fma(-nf, 1.90821492927058770002e-10, r);
     double p = 1.6059043836821613e-10;
-    p = horner(p, r, CPMPC_C64(8, 2.08767569878680989792e-09));
-    p = horner(p, r, CPMPC_C64(9, 2.50521083854417187751e-08));
-    p = horner(p, r, CPMPC_C64(10, 2.75573192239858906526e-07));
-    p = horner(p, r, CPMPC_C64(11, 2.75573192239858906526e-06));
-    p = horner(p, r, CPMPC_C64(12, 2.48015873015873015873e-05));
-    p = horner(p, r, CPMPC_C64(13, 1.98412698412698412698e-04));
-    p = horner(p, r, CPMPC_C64(14, 1.38888888888888888889e-03));
-    p = horner(p, r, CPMPC_C64(15, 8.33333333333333333333e-03));
-    p = horner(p, r, CPMPC_C64(16, 4.16666666666666666667e-02));
-    p = horner(p, r, CPMPC_C64(17, 1.66666666666666666667e-01));
-    p = horner(p, r, CPMPC_C64(18, 0.5));
+    p = horner(p, r, kCoef64[8]);
+    p = horner(p, r, kCoef64[9]);
+    p = horner(p, r, kCoef64[10]);
+    p = horner(p, r, kCoef64[11]);
+    p = horner(p, r, kCoef64[12]);
+    p = horner(p, r, kCoef64[13]);
+    p = horner(p, r, kCoef64[14]);
+    p = horner(p, r, kCoef64[15]);
+    p = horner(p, r, kCoef64[16]);
+    p = horner(p, r, kCoef64[17]);
+    p = horner(p, r, kCoef64[18]);
     p = ::fma(r * r, p, r);
     const double two_n = ::ldexp(1.0, (int)nf);
     const double t = ::fma(two_n, p, two_n - 1.0);
@@ -274,15 +212,15 @@ struct Math<double> {
     const double q = 0.25 * d;
     const double z = q * q;
     double sp = ::fma(z, -2.50521083854417187751e-08, 2.75573192239858906526e-06);  // -1/11!, 1/9!
-    sp = horner(sp, z, CPMPC_C64(19, -1.98412698412698412698e-04));                                // -1/7!
-    sp = horner(sp, z, CPMPC_C64(15, 8.33333333333333333333e-03));                                 // 1/5!
-    sp = horner(sp, z, CPMPC_C64(20, -1.66666666666666666667e-01));                                // -1/3!
+    sp = horner(sp, z, kCoef64[19]);  // -1/7!
+    sp = horner(sp, z, kCoef64[15]);  // 1/5!
+    sp = horner(sp, z, kCoef64[20]);  // -1/3!
     double sd = ::fma(q * z, sp, q);                                                // sin(d/4)
     double cp = ::fma(z, 2.08767569878680989792e-09, -2.75573192239858906526e-07);  // 1/12!, -1/10!
-    cp = horner(cp, z, CPMPC_C64(12, 2.48015873015873015873e-05));                                 // 1/8!
-    cp = horner(cp, z, CPMPC_C64(21, -1.38888888888888888889e-03));                                // -1/6!
-    cp = horner(cp, z, CPMPC_C64(16, 4.16666666666666666667e-02));                                 // 1/4!
-    cp = horner(cp, z, CPMPC_C64(22, -0.5));                                                       // -1/2!
+    cp = horner(cp, z, kCoef64[12]);  // 1/8!
+    cp = horner(cp, z, kCoef64[21]);  // -1/6!
+    cp = horner(cp, z, kCoef64[16]);  // 1/4!
+    cp = horner(cp, z, kCoef64[22]);  // -1/2!
     double cm1 = z * cp;                                                            // cos(d/4) - 1
 #pragma unroll
     for (int dbl = 0; dbl < 2; ++dbl) {  // a -> 2a
@@ -294,26 +232,9 @@ struct Math<double> {
     s = s0 + ::fma(c0, sd, s0 * cm1);
     c = c0 + ::fma(-s0, sd, c0 * cm1);
   }
-#endif
-#ifndef CPMPC_F64_TRIG_ROTATE
-#define CPMPC_F64_TRIG_ROTATE 1  // 0: a full sincos at every RK4 stage (A/B of the rotation above)
-#endif
-#ifndef CPMPC_F64_MERGED_RCP
-#define CPMPC_F64_MERGED_RCP 1   // 0: tanh's quotient and 1/den by two separate Newton chains (A/B)
-#endif
-  static constexpr bool kIncrementalTrig = CPMPC_F64_TRIG_ROTATE && !CPMPC_F64_LIBM;
-  static constexpr bool kMergedReciprocals = CPMPC_F64_MERGED_RCP && !CPMPC_F64_LIBM && !CPMPC_F64_IEEE_DIV;
+  static constexpr bool kIncrementalTrig = true;    // stages 2-4 rotate from stage 1's pair (sincos_delta)
+  static constexpr bool kMergedReciprocals = true;  // tanh's quotient and 1/den share one Newton chain (tanh_parts)
   static __device__ __forceinline__ double tanh_scaled(double x, double scale, double) { return tanh(x * scale); }
-#if CPMPC_F64_LIBM || CPMPC_F64_IEEE_DIV
-  static __device__ __forceinline__ double sqrt(double x) { return ::sqrt(x); }
-  static __device__ __forceinline__ double rcp(double x) { return 1.0 / x; }
-  static __device__ __forceinline__ double div(double a, double b) { return a / b; }
-  static __device__ __forceinline__ void sqrt_inv(double x, double& s, double& r) {
-    s = ::sqrt(x);
-    r = (0.0 < s) ? 1.0 / s : 0.0;
-  }
-  static __device__ __forceinline__ double sqrt_only(double x) { return ::sqrt(x); }
-#else
   // The compiler's IEEE division is 11 instructions around v_rcp_f64 (two v_div_scale, four refinement fma, the
   // quotient and its residual, v_div_fmas, v_div_fixup) and its sqrt 15 around v_rsq_f64 (range scaling either side);
   // an RK4 stage holds three reciprocals and a square root.  The operands here are ordinary magnitudes (no scaling
@@ -373,7 +294,6 @@ struct Math<double> {
     const double h1 = ::fma(h, e, h);
     return ::fma(::fma(-g, g, xm), h1, g);
   }
-#endif
   static __device__ __forceinline__ double fabs(double x) { return ::fabs(x); }
   static __device__ __forceinline__ double trunc(double x) { return ::trunc(x); }
   static __device__ __forceinline__ double fma(double a, double b, double c) { return ::fma(a, b, c); }
@@ -576,15 +496,16 @@ __device__ __forceinline__ void cartpole_accel(const CartPoleConsts<R>& k, const
   cartpole_accel_sc<R, WITH_J, HAS_EXT>(k, bx, s, c, v, w, u, fe, a_x, a_th, Ja, Jua);
 }
 
-// The pole angle's sine and cosine across the stages of an RK4 step and the steps of a rollout: the first step's stage 1
-// evaluates them in full and keeps the base; everything after is a rotation away (Math<R>::sincos_delta) unless a lane
-// moves further than the kernels cover (|d| > 1 rad within one step: a pole at more than 100 rad/s, or a wrapped angle),
-// which takes the full path for that lane.
+// The pole angle's sine and cosine across the stages of an RK4 step: stage 1 evaluates them in full and keeps the base;
+// stages 2-4 are a rotation away (Math<R>::sincos_delta) unless a lane moves further than the kernels cover (|d| > 1 rad
+// within one step: a pole at more than 100 rad/s), which takes the full path for that lane.
 template <typename R>
 struct TrigBase {
   R th0, s0, c0;
-  bool valid = false;  // (th0, s0, c0) hold the previous step's stage-1 pair: this step's stage 1 may rotate from it
-  __device__ __forceinline__ void invalidate() { valid = false; }  // the next stage 1 evaluates in full (re-anchors the chain)
+  // Written by stage 1 and invalidate(), read by nothing since stage 1 always evaluates in full (stage_sincos).  Kept, with
+  // the invalidate() calls of the split kernels, only because dropping the dead stores changes their register allocation.
+  bool valid = false;
+  __device__ __forceinline__ void invalidate() { valid = false; }
 };
 // The far branch of a rotation (|d| > 1 rad, or a NaN) is taken per LANE, never per wave: a problem's arithmetic must
 // not depend on what its neighbours in the wave do (batch-position independence: staged, sharded and stand-alone solves
@@ -593,30 +514,16 @@ template <typename R>
 __device__ __forceinline__ void sincos_from_base(const TrigBase<R>& tb, const R th, R& s, R& c) {
   const R d = th - tb.th0;
   Math<R>::sincos_delta(tb.s0, tb.c0, d, s, c);
-#ifndef CPMPC_F64_TRIG_NO_FALLBACK  // (defined only to count the main path's instructions in a listing)
   if (__builtin_expect(!(Math<R>::fabs(d) <= R(1)), 0)) Math<R>::sincos(th, s, c);
-#endif
 }
-// 0 (default): stage 1 of every RK4 step evaluates sine and cosine in full.  1: stage 1 rotates from the previous step's
-// pair when there is one (round 3: the branch on the loop-carried flag and the second code path cost more than the 19
-// instructions saved, 48.9 against 49.9 M re-plans/s).  2 (round 5): the same, and the fused kernel's two rollouts evaluate
-// the base in full BEFORE their loops (Model::chain_begin), so that inside them the flag is a constant and stage 1 is
-// always a rotation -- no branch, one code path.
-#ifndef CPMPC_F64_TRIG_CHAIN
-#define CPMPC_F64_TRIG_CHAIN 0
-#endif
-template <typename R, int STAGE, int CHAIN = CPMPC_F64_TRIG_CHAIN>
+// Stage 1 of every RK4 step evaluates sine and cosine in full.  Rotating it from the previous step's pair as well did not
+// pay: behind a per-step flag 48.9 against 49.9 M re-plans/s (round 3); with the base evaluated once before each rollout
+// of the fused kernel +0.5 %, below the 1.5 % bar (round 5), and -1 % for the 6-state model (round 6).
+template <typename R, int STAGE>
 __device__ __forceinline__ void stage_sincos(TrigBase<R>& tb, const R th, R& s, R& c) {
   if constexpr (Math<R>::kIncrementalTrig) {
     if constexpr (STAGE == 1) {
-      // consecutive steps of one rollout: this step's angle is within h |w| of the previous step's, so stage 1 rotates
-      // from that pair too (one more rotation per step: the chain's error grows like the square root of its length,
-      // ~1.5 ulp over the ten steps of an interval); a wrapped angle jumps by 2 pi and takes the far branch
-      if (CHAIN && tb.valid) {
-        sincos_from_base<R>(tb, th, s, c);
-      } else {
-        Math<R>::sincos(th, s, c);
-      }
+      Math<R>::sincos(th, s, c);
       tb.th0 = th;
       tb.s0 = s;
       tb.c0 = c;

@@ -227,9 +227,9 @@ static int create_impl(const cpmpc_params* params, const cpmpc_solver_opts* opts
   s->dtype = dtype;
   s->beyond_parity = (double)params->window_length * params->control_dt > kMaxParityHorizon * (1.0 + 1e-9);
   // default: refine where the control cost is weak (measured: include/cpmpc.h, CPMPC_CREATE_REFINE_QP) and, since round 6,
-  // beyond the parity horizon: there one pass of refinement with residuals from the original data takes the lanes on
-  // which the kernels (not the CPU check) moved from 34 of 8 192 to 3 at N = 160 (profiles/r06_long_horizon_probe.json);
-  // further passes change nothing (the refined solve and a dense pivoted one are then both at the problem's conditioning)
+  // beyond the parity horizon: there AUTO takes the split pipeline with two passes of refinement with residuals from the
+  // original data (refine_passes below), and the lanes on which the kernels (not the CPU check) are at fault go from 34 of
+  // 8 192 to 1 at N = 160, as many as the CPU check (profiles/r06_long_horizon_probe_{8192,16384}.json)
   s->refine_qp = (flags & CPMPC_CREATE_REFINE_QP) != 0 ||
                  (!(flags & CPMPC_CREATE_NO_REFINE_QP) && (params->u_cost_weight < kRefineBelowUCostWeight || s->beyond_parity));
   // split pipeline: one pass; two beyond the parity horizon (tools/long_horizon_refine_study.py, first QP of 300 cold starts at
@@ -877,8 +877,6 @@ static bool host_ptr_is_pinned(const void* p) {
 // behind the kernels and the strided device-to-host copies are not (measured, profiles/r04_host_path.json).
 static bool host_direct_outputs(const cpmpc_solver* s, const cpmpc_step_host_outputs& out) {
   if (s->dtype != CPMPC_F64 || out.predicted == nullptr) return false;
-  if (const char* e = getenv("CPMPC_HOST_DIRECT"))  // measurement switch: 0 = always through the mirror
-    if (e[0] == '0') return false;
   if (!host_ptr_is_pinned(out.predicted) || !host_ptr_is_pinned(out.u)) return false;
   if (out.solution && !host_ptr_is_pinned(out.solution)) return false;
   return true;

@@ -118,12 +118,6 @@ static void launch_linearize(const SolverArgs<R, M>& a, int SP, const XV<R, M::N
 #undef CPMPC_LIN
 }
 
-// 1: the fp64 fused kernels also take batch-shared model constants from the kernel-argument segment (SGPRs).  Off by
-// default: see the note above launch_fused (tools/_build variant `shared64` measures it).
-#ifndef CPMPC_FUSED_SHARED_F64
-#define CPMPC_FUSED_SHARED_F64 0
-#endif
-
 // The shared-parameters specialisation (model constants wave-uniform, in SGPRs) is used in fp32 only: the fp64
 // kernel already sits at the SGPR limit with its VGPR/AGPR file exhausted, and with the constants added to the
 // scalar pressure hipcc 7.2 produced wrong results for it (caught by the fp64 parity tests); there the constants
@@ -137,13 +131,11 @@ static void launch_fused(const SolverArgs<R, M>& a, int L, int SP, int max_iters
     // QP in double (CPMPC_CREATE_WIDE_QP); constants through vector registers there (SHARED = false)
 #define CPMPC_FUSED(LV, SPV)                                                                                \
   if (L == LV && SP == SPV) {                                                                               \
-    { /* double: REFINE_QP; float: WIDE_QP */                                                               \
-      if (refine) {                                                                                         \
-        hipLaunchKernelGGL((fused_sqp_kernel<R, M, SPV, LV, false, true>), grid, dim3(64), 0, stream, a, max_iters); \
-        return;                                                                                             \
-      }                                                                                                     \
+    if (refine) {                                                                                           \
+      hipLaunchKernelGGL((fused_sqp_kernel<R, M, SPV, LV, false, true>), grid, dim3(64), 0, stream, a, max_iters); \
+      return;                                                                                               \
     }                                                                                                       \
-    if constexpr (sizeof(R) == 4 || CPMPC_FUSED_SHARED_F64) {                                              \
+    if constexpr (sizeof(R) == 4) {                                                                         \
       if (a.dyn == nullptr) {                                                                               \
         hipLaunchKernelGGL((fused_sqp_kernel<R, M, SPV, LV, true, false>), grid, dim3(64), 0, stream, a, max_iters); \
         return;                                                                                             \
@@ -164,13 +156,11 @@ static void launch_fused(const SolverArgs<R, M>& a, int L, int SP, int max_iters
     const size_t lds = fused_dyn_lds_bytes<R, M>(SP);
 #define CPMPC_FUSED_DYN(LV)                                                                                         \
   if (L == LV) {                                                                                                    \
-    { /* double: REFINE_QP; float: WIDE_QP */                                                                       \
-      if (refine) {                                                                                                 \
-        hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, LV, false, true>), grid, dim3(64), lds, stream, a, max_iters); \
-        return;                                                                                                     \
-      }                                                                                                             \
+    if (refine) {                                                                                                   \
+      hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, LV, false, true>), grid, dim3(64), lds, stream, a, max_iters); \
+      return;                                                                                                       \
     }                                                                                                               \
-    if constexpr (sizeof(R) == 4 || CPMPC_FUSED_SHARED_F64) {                                                      \
+    if constexpr (sizeof(R) == 4) {                                                                                 \
       if (a.dyn == nullptr) {                                                                                       \
         hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, LV, true, false>), grid, dim3(64), lds, stream, a, max_iters); \
         return;                                                                                                     \
@@ -223,7 +213,7 @@ static int step_batch_impl(cpmpc_solver* s, int64_t B, const cpmpc_step_inputs* 
   // (the first compaction's counter: cleared by prepare_kernel whether or not this step turns out to be staged)
   a.stage_count0 = (use_fused(s) && s->active != nullptr) ? s->active + s->cap + 3 * slot : nullptr;
   span_begin(s, CPMPC_KERNEL_PREPARE, stream, &sp);
-  hipLaunchKernelGGL((prepare_kernel<R, M>), dim3((unsigned)((B + CPMPC_PF_BLOCK - 1) / CPMPC_PF_BLOCK)), dim3(CPMPC_PF_BLOCK), 0, stream, a);
+  hipLaunchKernelGGL((prepare_kernel<R, M>), dim3((unsigned)((B + kPfBlock - 1) / kPfBlock)), dim3(kPfBlock), 0, stream, a);
   span_end(s, stream, &sp);
 
   if (use_fused(s)) {
@@ -282,7 +272,7 @@ static int step_batch_impl(cpmpc_solver* s, int64_t B, const cpmpc_step_inputs* 
   // the histogram of iterations per problem goes back to the host for the plan of a later step (default staging only)
   if (use_fused(s) && s->stage_auto && s->fb_host != nullptr && s->active != nullptr &&
       (s->params.relative_exit_tol > 0.0 || s->params.absolute_first_derivative_tol > 0.0)) {
-    const int64_t groups = (B + CPMPC_PF_BLOCK - 1) / CPMPC_PF_BLOCK;
+    const int64_t groups = (B + kPfBlock - 1) / kPfBlock;
     a.fb_stride = (int)((groups + kFbReporters - 1) / kFbReporters);
     a.fb_host = s->fb_host_dev + (size_t)slot * kFbReporters * (kFbBins + 1);
     // sequence numbers 1 .. 2^30 and round again (0 = "no report yet"); compared modulo 2^30 in cpmpc_plan_stages
@@ -291,7 +281,7 @@ static int step_batch_impl(cpmpc_solver* s, int64_t B, const cpmpc_step_inputs* 
     s->fb_reporters[slot] = (int)((groups + a.fb_stride - 1) / a.fb_stride);
   }
   span_begin(s, CPMPC_KERNEL_FINALIZE, stream, &sp);
-  hipLaunchKernelGGL((finalize_kernel<R, M>), dim3((unsigned)((B + CPMPC_PF_BLOCK - 1) / CPMPC_PF_BLOCK)), dim3(CPMPC_PF_BLOCK), 0, stream, a);
+  hipLaunchKernelGGL((finalize_kernel<R, M>), dim3((unsigned)((B + kPfBlock - 1) / kPfBlock)), dim3(kPfBlock), 0, stream, a);
   span_end(s, stream, &sp);
 
   HIP_TRY(hipGetLastError());

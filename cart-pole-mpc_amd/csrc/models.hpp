@@ -44,14 +44,6 @@ struct SingleModelHandWritten {
   }
   // the same at stage STAGE (1..4) of an RK4 step, with what the stages can share (the pole angle's sine and cosine)
   using StepCache = TrigBase<R>;
-  // before the first step of a rollout from x (CPMPC_F64_TRIG_CHAIN = 2: the base pair in full, once per rollout)
-  __device__ __forceinline__ static void chain_begin(StepCache& sc, const R (&x)[NX]) {
-    if constexpr (Math<R>::kIncrementalTrig && CPMPC_F64_TRIG_CHAIN == 2) {
-      Math<R>::sincos(x[1], sc.s0, sc.c0);
-      sc.th0 = x[1];
-      sc.valid = true;
-    }
-  }
   template <bool WITH_J, bool HAS_EXT, int STAGE>
   __device__ __forceinline__ static void accel_stage(const Consts& k, const R (&x)[NX], const R u,
                                                      const ExtForce<R>& fe, R (&a)[NQ], R (&Ja)[NQ][NX],
@@ -140,13 +132,6 @@ struct SingleModelGenerated {
     accel_sc<WITH_J, HAS_EXT>(k, s, c, x, u, fe, a, Ja, Jua);
   }
   using StepCache = TrigBase<R>;
-  __device__ __forceinline__ static void chain_begin(StepCache& sc, const R (&x)[NX]) {
-    if constexpr (Math<R>::kIncrementalTrig && CPMPC_F64_TRIG_CHAIN == 2) {
-      Math<R>::sincos(x[1], sc.s0, sc.c0);
-      sc.th0 = x[1];
-      sc.valid = true;
-    }
-  }
   template <bool WITH_J, bool HAS_EXT, int STAGE>
   __device__ __forceinline__ static void accel_stage(const Consts& k, const R (&x)[NX], const R u,
                                                      const ExtForce<R>& fe, R (&a)[NQ], R (&Ja)[NQ][NX],
@@ -175,19 +160,9 @@ using SingleModel = SingleModelHandWritten<R>;
 // get both pairs by one rotation each from stage 1's (StepCache = two TrigBase: 8 full fp64 sincos per step -> 2); entries
 // of dF/dx and dM/dth that vanish identically are neither written nor read (DoublePendulumGenSparsity), and the columns of
 // da/dx that vanish identically -- b_x and b_x' do not enter these dynamics -- are known to the RK4 sensitivity chain
-// (kJaZeroCols: a third of its multiply-adds were products with those zeros).
+// (kJaZeroCols: a third of its multiply-adds were products with those zeros; 3.7 % of the fp64 kernel time).  The rotation
+// is worth 5 % in fp64 (fp32 has v_sin_f32).
 // ------------------------------------------------------------------------------------------------
-#ifndef CPMPC_DOUBLE_TRIG_ROTATE
-#define CPMPC_DOUBLE_TRIG_ROTATE 1   // 0: a full sincos of both angles at every RK4 stage (A/B)
-#endif
-// as CPMPC_F64_TRIG_CHAIN (cartpole_device.hpp) for this model: 2 = the rollouts of the fused kernel evaluate both base pairs in
-// full once (chain_begin) and stage 1 of every step rotates from the previous step's pair
-#ifndef CPMPC_DOUBLE_TRIG_CHAIN
-#define CPMPC_DOUBLE_TRIG_CHAIN 0
-#endif
-#ifndef CPMPC_JA_ZERO_COLS
-#define CPMPC_JA_ZERO_COLS 1         // 0: the sensitivity chain multiplies through the identically-zero columns (A/B)
-#endif
 template <typename R>
 struct DoubleConsts {
   DoublePendulumGenConsts<R> g;  // generated: coefficients of the terms
@@ -204,7 +179,7 @@ struct DoubleModel {
   static constexpr int NX = 6, NQ = 3, NP = 6;
   using Consts = DoubleConsts<R>;
   using Sp = DoublePendulumGenSparsity;
-  static constexpr unsigned kJaZeroCols = CPMPC_JA_ZERO_COLS ? Sp::ja_zero_cols : 0u;
+  static constexpr unsigned kJaZeroCols = Sp::ja_zero_cols;
   template <typename P>
   __host__ __device__ static Consts make(const P* p) {
     Consts k;
@@ -294,27 +269,14 @@ struct DoubleModel {
   }
   // what the stages of an RK4 step (and consecutive steps of a rollout) share: both poles' sine / cosine pairs
   using StepCache = DoubleTrig<R>;
-  __device__ __forceinline__ static void chain_begin(StepCache& sc, const R (&x)[NX]) {
-    if constexpr (Math<R>::kIncrementalTrig && CPMPC_DOUBLE_TRIG_ROTATE && CPMPC_DOUBLE_TRIG_CHAIN == 2) {
-      Math<R>::sincos(x[1], sc.t1.s0, sc.t1.c0);
-      Math<R>::sincos(x[2], sc.t2.s0, sc.t2.c0);
-      sc.t1.th0 = x[1];
-      sc.t2.th0 = x[2];
-      sc.t1.valid = sc.t2.valid = true;
-    }
-  }
   template <bool WITH_J, bool HAS_EXT, int STAGE>
   __device__ __forceinline__ static void accel_stage(const Consts& k, const R (&x)[NX], const R u,
-                                                     const ExtForce<R>& fe, R (&a)[NQ], R (&Ja)[NQ][NX],
+                                                     const ExtForce<R>&, R (&a)[NQ], R (&Ja)[NQ][NX],
                                                      R (&Jua)[NQ], StepCache& sc) {
-    if constexpr (CPMPC_DOUBLE_TRIG_ROTATE) {
-      R s1, c1, s2, c2;
-      stage_sincos<R, STAGE, CPMPC_DOUBLE_TRIG_CHAIN>(sc.t1, x[1], s1, c1);
-      stage_sincos<R, STAGE, CPMPC_DOUBLE_TRIG_CHAIN>(sc.t2, x[2], s2, c2);
-      accel_sc<WITH_J>(k, s1, c1, s2, c2, x, u, a, Ja, Jua);
-    } else {
-      accel<WITH_J, HAS_EXT>(k, x, u, fe, a, Ja, Jua);
-    }
+    R s1, c1, s2, c2;
+    stage_sincos<R, STAGE>(sc.t1, x[1], s1, c1);
+    stage_sincos<R, STAGE>(sc.t2, x[2], s2, c2);
+    accel_sc<WITH_J>(k, s1, c1, s2, c2, x, u, a, Ja, Jua);
   }
 };
 
@@ -337,8 +299,7 @@ __host__ __device__ constexpr bool is_angle(int t) {
 // ------------------------------------------------------------------------------------------------
 // RK4 without sensitivities (integration.hpp:52-62).  x updated in place.
 // ------------------------------------------------------------------------------------------------
-// `sc` carries what consecutive steps of one rollout can share (models.hpp: StepCache): pass the same object to every
-// step of the rollout, start a new rollout with a fresh object (or sc.invalidate()).
+// `sc` carries what the stages of the step share (models.hpp: StepCache).
 template <typename R, typename M, bool HAS_EXT>
 __device__ __forceinline__ void rk4_step_m(const typename M::Consts& k, const R h, R (&x)[M::NX], const R u,
                                            const ExtForce<R>& fe, typename M::StepCache& sc) {
@@ -395,7 +356,8 @@ __host__ __device__ constexpr int first_nonzero_col(unsigned zmask) {
 // dynamics (zmask bit c: Ja[:, c] = 0 at every stage) gives, by D_1 = K_1, D_{j+1} = K_{j+1} (I + a_j D_j):
 //   a position c < NQ:                                   D_j[:, c] = 0       for every stage,  A[:, c] = e_c
 //   a velocity c = NQ + r whose position r is such too:  D_j[:, c] = e_r     for every stage,  A[:, c] = e_c + h e_r
-// so the chain neither computes nor stores those columns, and products with A take them as the 0, 1 and h they are.
+// so the chain neither computes nor stores those columns, and products with A take them as the 0, 1 and h they are
+// (round 6: 5 % of the fp64 and 4 % of the fp32 6-state kernel time).
 template <int NX, int NQ>
 __host__ __device__ constexpr unsigned trivial_cols(unsigned zmask) {
   unsigned t = 0;
@@ -405,9 +367,6 @@ __host__ __device__ constexpr unsigned trivial_cols(unsigned zmask) {
   }
   return t;
 }
-#ifndef CPMPC_JA_TRIVIAL_COLS
-#define CPMPC_JA_TRIVIAL_COLS 1   // 0: the chain carries the identically-known columns like any other (A/B)
-#endif
 // The pattern those columns leave in every product of step Jacobians (Phi of an interval, Psi = diag(w) Phi ... Phi across
 // intervals): in a trivial column c only row c and, for a velocity, row c - NQ can be non-zero -- A[:, c] = e_c (+ h e_{c-NQ}),
 // and the pattern is closed under the product (its c - NQ is a trivial position column, whose only row is itself).  Entry
@@ -431,7 +390,7 @@ __device__ __forceinline__ void stage_chain_m(const R (&Ja)[NQ][NX], const R (&J
                                               const R (&D)[NX][NX], const R (&d)[NX], R (&Dn)[NX][NX],
                                               R (&dn)[NX]) {
   constexpr int k0 = first_nonzero_col<NX>(ZMASK);
-  constexpr unsigned TRIV = CPMPC_JA_TRIVIAL_COLS ? trivial_cols<NX, NQ>(ZMASK) : 0u;
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(ZMASK);
 #pragma unroll
   for (int c = 0; c < NX; ++c) {
     if ((TRIV >> c) & 1u) continue;  // known in closed form: neither computed nor stored
@@ -466,7 +425,7 @@ __device__ __forceinline__ void stage_chain_first_m(const R (&Ja)[NQ][NX], const
                                                     const R (&Ja1)[NQ][NX], const R (&Jua1)[NQ], R (&Dn)[NX][NX],
                                                     R (&dn)[NX]) {
   // D_1's rows: top r = e_{NQ + r}, bottom r = Ja1[r].  (Ja D_1)[r][c] = sum_kk<NQ Ja[r][kk] [c == NQ + kk] + sum_kk Ja[r][NQ + kk] Ja1[kk][c]
-  constexpr unsigned TRIV = CPMPC_JA_TRIVIAL_COLS ? trivial_cols<NX, NQ>(ZMASK) : 0u;
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(ZMASK);
 #pragma unroll
   for (int c = 0; c < NX; ++c) {
     if ((TRIV >> c) & 1u) continue;
@@ -507,17 +466,13 @@ __device__ __forceinline__ void stage_chain_first_m(const R (&Ja)[NQ][NX], const
   }
 }
 
-#ifndef CPMPC_RK4_STAGE2_STRUCTURED
-#define CPMPC_RK4_STAGE2_STRUCTURED 1
-#endif
-
 template <typename R, typename M, bool HAS_EXT>
 __device__ __forceinline__ void rk4_step_jac_m(const typename M::Consts& k, const R h, R (&x)[M::NX],
                                                const R u, const ExtForce<R>& fe, R (&A)[M::NX][M::NX],
                                                R (&Bv)[M::NX], typename M::StepCache& sc) {
   constexpr int NX = M::NX, NQ = M::NQ;
   constexpr unsigned ZM = JaZeroCols<M>::value;
-  constexpr unsigned TRIV = CPMPC_JA_TRIVIAL_COLS ? trivial_cols<NX, NQ>(ZM) : 0u;
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(ZM);
   const R hh = h / R(2);
   R Ja[NQ][NX], Jua[NQ];
   R D[NX][NX], d[NX], Dn[NX][NX], dn[NX];
@@ -552,7 +507,6 @@ __device__ __forceinline__ void rk4_step_jac_m(const typename M::Consts& k, cons
     xt[i] = x[i] + x[NQ + i] * hh;
     xt[NQ + i] = v2[i];
   }
-#if CPMPC_RK4_STAGE2_STRUCTURED
   {
     R Ja1[NQ][NX], Jua1[NQ];
 #pragma unroll
@@ -564,10 +518,6 @@ __device__ __forceinline__ void rk4_step_jac_m(const typename M::Consts& k, cons
     M::template accel_stage<true, HAS_EXT, 2>(k, xt, u, fe, a2, Ja, Jua, sc);
     stage_chain_first_m<R, NX, NQ, ZM>(Ja, Jua, hh, Ja1, Jua1, Dn, dn);
   }
-#else
-  M::template accel_stage<true, HAS_EXT, 2>(k, xt, u, fe, a2, Ja, Jua, sc);
-  stage_chain_m<R, NX, NQ, ZM>(Ja, Jua, hh, D, d, Dn, dn);
-#endif
 #pragma unroll
   for (int r = 0; r < NX; ++r) {
 #pragma unroll
@@ -633,7 +583,7 @@ __device__ __forceinline__ void rk4_step_jac_m(const typename M::Consts& k, cons
 template <typename R, typename M>
 __device__ __forceinline__ void step_jac_apply(const R (&A)[M::NX][M::NX], const R h, const R (&v)[M::NX], R (&y)[M::NX]) {
   constexpr int NX = M::NX, NQ = M::NQ;
-  constexpr unsigned TRIV = CPMPC_JA_TRIVIAL_COLS ? trivial_cols<NX, NQ>(JaZeroCols<M>::value) : 0u;
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);
 #pragma unroll
   for (int r = 0; r < NX; ++r) {
     bool have = false;

@@ -69,18 +69,11 @@ __device__ __forceinline__ Mat2<R> mat2_pow_rt(const Mat2<R>& t, int e) {  // ru
 // row shifts and, for L = 4 (one quad) and L = 2, sums and broadcasts are quad permutes.  DPP moves are VALU
 // operand modifiers: no trip through the LDS crossbar as for ds_bpermute (__shfl), which matters in the
 // boundary chains where every move is on the critical path.
-#ifndef CPMPC_DPP_NO_OLD
-#define CPMPC_DPP_NO_OLD 1
-#endif
 template <int CTRL>
 __device__ __forceinline__ int dpp32(int v) {
-#if CPMPC_DPP_NO_OLD
   // every lane is written (all rows and banks enabled; a lane whose source falls off its row reads 0), so there is no
   // previous value to preserve and no `v_mov_b32 dst, 0` in front of the move
   return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
-#else
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-#endif
 }
 template <int CTRL>
 __device__ __forceinline__ float dpp(float v) {
@@ -168,49 +161,10 @@ __device__ __forceinline__ R group_last(R v, int gbase) {
 // Waves per SIMD the register allocator must leave room for.  The sweeps are latency chains (LDS round trips,
 // lane shuffles), so a second resident wave is worth a few spilled dwords in fp32 (measured +15%); fp64 values
 // take two registers each and stay at one wave.
-#ifndef CPMPC_FUSED_WAVES_F32
-#define CPMPC_FUSED_WAVES_F32 2
-#endif
-// 1 (default): the fp32 fused kernel also refines the terminal multipliers once through the factored operator (the
-// fp64 one always does); 0 builds the A/B variant without it (tools: build_variant("norefine32", ...))
-#ifndef CPMPC_FUSED_REFINE_F32
-#define CPMPC_FUSED_REFINE_F32 1
-#endif
-// refinement passes in a float kernel whose terminal system is carried in double (wide.hpp; measured in round 4)
-#ifndef CPMPC_FUSED_REFINE_WIDE
-#define CPMPC_FUSED_REFINE_WIDE 0
-#endif
-// refinement passes of the terminal multipliers for horizons of more than four intervals (fp64)
-#ifndef CPMPC_FUSED_REFINE_LONG
-#define CPMPC_FUSED_REFINE_LONG 2
-#endif
-// the Gamma update loop of the linearisation reads one column ahead (default: fp64 only; -DCPMPC_FUSED_GAMMA_AHEAD_ALL=0/1
-// forces it off / on for both dtypes)
-#ifdef CPMPC_FUSED_GAMMA_AHEAD_ALL
-#define CPMPC_FUSED_GAMMA_AHEAD(R) (CPMPC_FUSED_GAMMA_AHEAD_ALL != 0)
-#else
-#define CPMPC_FUSED_GAMMA_AHEAD(R) (sizeof(R) == 8)
-#endif
+constexpr int kFusedWavesF32 = 2;
+#define CPMPC_FUSED_BOUNDS __launch_bounds__(64, ((sizeof(R) == 4 && M::NX <= 4) ? kFusedWavesF32 : 1))
 // unroll factor of the block-local sweep passes (LDS reads of several controls in flight)
-// The exit test's rounding floor (cpmpc_solver_opts.exit_defect_floor) in the DOUBLE kernels: left out by default.  In
-// double the floor is 3e-14 -- it could change an exit decision only where |D| is within mu x 3e-14 of the tolerance -- and
-// carrying the few instructions costs the fp64 fused kernel 1.6 % (4.845 -> 4.925 ms at B = 262 144, same-session A/B: the
-// kernel sits at its register limit and the extra live values reshuffle its spills).  1 compiles it in.
-#ifndef CPMPC_EXIT_FLOOR_F64
-#define CPMPC_EXIT_FLOOR_F64 0
-#endif
-// 1: the float 4-state kernels carry the whole terminal part of the QP in double (mpc_fused_body.inc: kWideQP); measured in
-// round 5, see HISTORY.md
-#ifndef CPMPC_FUSED_WIDE_QP_F32
-#define CPMPC_FUSED_WIDE_QP_F32 0
-#endif
-#ifndef CPMPC_SWEEP_UNROLL
-#define CPMPC_SWEEP_UNROLL 5
-#endif
-#ifndef CPMPC_FUSED_EXTRA_ATTR
-#define CPMPC_FUSED_EXTRA_ATTR  // experiments: e.g. -DCPMPC_FUSED_EXTRA_ATTR='__attribute__((amdgpu_num_vgpr(168)))'
-#endif
-#define CPMPC_FUSED_BOUNDS __launch_bounds__(64, ((sizeof(R) == 4 && M::NX <= 4) ? CPMPC_FUSED_WAVES_F32 : 1))
+constexpr int kFusedSweepUnroll = 5;
 
 // Debug build only (-DCPMPC_FUSED_TIMING): shader-clock cycles per phase, summed over waves, read back by
 // cpmpc_debug_phase_cycles().  Not part of the product library.
@@ -260,60 +214,26 @@ static __device__ unsigned long long g_fused_clock[4];  // sum of shader cycles,
 #define CPMPC_CLOCK_END() do { } while (0)
 #endif
 
-// Lean LDS layout, an experiment kept as a build option (round 3, measured negative, default off).  Motivation
-// (tools/ubench/clock.hip): ONE wave issues a vector instruction every ~5.1 cycles at best, so the two waves per SIMD the
-// fp32 kernel runs keep a 2-cycle issue port 39 % busy and a third would saturate it.  Three waves need <= 168 registers
-// (costs this kernel 24 spilled values, none inside a loop) and less LDS: with (U^-1 g)_k sharing the slot of du_k (the
-// previous step is dead when sweep 1 writes it; sweep 1b turns it into v_k in place) a wave needs 17.5 KB instead of 20
-// and nine fit a CU instead of eight (-DCPMPC_FUSED_LEAN_LDS=1): measured 108.4 M re-plans/s against 116.3 M; with the
-// 1/d_k of a lane's controls in registers as well (15 KB, ten waves per CU, -DCPMPC_FUSED_ID_REGS=1) the fully unrolled
-// sweeps spill 109-151 values: 99.0 M.  A third wave on one or two of a CU's four SIMDs does not pay for the registers
-// it takes from the other two.
-#ifndef CPMPC_FUSED_LEAN_LDS
-#define CPMPC_FUSED_LEAN_LDS 0
-#endif
-template <typename R, typename M, int SP>
-__host__ __device__ constexpr bool fused_lean() {
-  return CPMPC_FUSED_LEAN_LDS && sizeof(R) == 4 && M::NX <= 4 && SP <= 10;
-}
-// Slim layout for the double kernel of the 6-state model (round 5): with (U^-1 g)_k in the slot of du_k (as in the lean
-// layout above) and the 1/d_k of a lane's controls in registers, a wave needs u + du + Gamma = (8 + 8 + 48) x SP x 64 bytes
-// = 40 KB at SP = 10 instead of 60 KB: four waves per CU -- one per SIMD, all the 512-register kernel can use -- instead of
-// two.  Not for the REFINE instantiation (its second solve needs gw and du side by side).
-// (Round 5 also tried the float 6-state kernel in this layout with a 256-register budget, two waves per SIMD: 533 spilled
-// dwords, 33 against 51 M re-plans/s; the option was removed in round 6, HISTORY.md has the numbers.)
-#ifndef CPMPC_FUSED_SLIM_F64_NX6
-#define CPMPC_FUSED_SLIM_F64_NX6 1
-#endif
+// Slim layout for the double kernel of the 6-state model (round 5): with (U^-1 g)_k in the slot of du_k (the previous step
+// is dead when sweep 1 writes it; sweep 1b turns it into v_k in place) and the 1/d_k of a lane's controls in registers, a
+// wave needs u + du + Gamma = (8 + 8 + 48) x SP x 64 bytes = 40 KB at SP = 10 instead of 60 KB: four waves per CU -- one per
+// SIMD, all the 512-register kernel can use -- instead of two.  Not for the REFINE instantiation
+// (its second solve needs gw and du side by side).  For a third wave per SIMD the fp32 4-state kernel with (U^-1 g)_k in the
+// slot of du_k measured 108.4 M re-plans/s against 116.3 M, and 99.0 M with the 1/d_k in registers too (round 3); the float
+// 6-state kernel in the slim layout at two waves per SIMD spilled 533 dwords, 33 against 51 M (round 5).
 template <typename R, typename M, int SP, bool REFINE>
 __host__ __device__ constexpr bool fused_slim() {
-  return CPMPC_FUSED_SLIM_F64_NX6 && sizeof(R) == 8 && M::NX > 4 && !REFINE && SP <= 10;
+  return sizeof(R) == 8 && M::NX > 4 && !REFINE && SP <= 10;
 }
-#undef CPMPC_FUSED_BOUNDS
-#define CPMPC_FUSED_BOUNDS_S __launch_bounds__(64, (fused_lean<R, M, SP>() ? 3 : ((sizeof(R) == 4 && M::NX <= 4) ? CPMPC_FUSED_WAVES_F32 : 1)))
-#define CPMPC_FUSED_BOUNDS __launch_bounds__(64, ((sizeof(R) == 4 && M::NX <= 4) ? CPMPC_FUSED_WAVES_F32 : 1))
 
 // ---- Gamma in LDS ---------------------------------------------------------------------------------------------------
-// A column of Gamma_s is an NX-vector: 16 bytes (float, NX = 4), 32 (double NX = 4; float NX = 6, padded) or 64 (double,
-// NX = 6).  Stored as one element per lane ([i * 64 + lane], rounds 1-3) the wider ones put consecutive lanes 32 / 64
-// bytes apart: by the bank rule of ds_read_b128 ((address / 4) mod 64 within its 16-lane groups, MI355X_MICROARCH.md
-// LDS section) lanes l and l + 8 of a group then share banks: a 2-way (4-way) conflict on every read and write of Gamma.
-// CPMPC_FUSED_G_PLANES = 1 stores the vector as 16-byte pieces in separate planes, [(i * pieces + p) * 64 + lane]:
-// lane-consecutive 16-byte slots, the conflict-free pattern.  Same bytes of LDS; float / NX = 4 is one piece either way.
-// Measured (round 4, fp64, B = 262 144, same session; profiles/r04_f64_{planes,noplanes}_pmc_summary.json):
-// SQ_LDS_BANK_CONFLICT 7 800 -> 0 cycles per wave (39 % of the LDS-array cycles gone, exactly the predicted 2-way), and the
-// kernel is 0.5 % SLOWER (4.832 vs 4.805 ms; 50.7 vs 50.95 M re-plans/s), SQ_WAIT_ANY unchanged (11.7 % vs 11.3 % of
-// wave-cycles), SQ_WAIT_INST_LDS 0.1 % in both: the LDS array works 3 % of the wave's cycles either way, so its conflicts
-// were never what the lone wave waits for, and the second address per access costs more than they did.  Default off.
-#ifndef CPMPC_FUSED_G_PLANES
-#define CPMPC_FUSED_G_PLANES 0
-#endif
-// Round 5: a column occupies only the pieces it fills -- 48 bytes instead of the padded 64 for double / NX = 6, 24 instead of
-// 32 for float / NX = 6 (CPMPC_FUSED_G_UNPADDED = 0 restores the padded elements): Gamma is 30 KB instead of 40 KB per wave
-// for the double 6-state kernel, three waves per CU instead of two (and four with the slim layout below).
-#ifndef CPMPC_FUSED_G_UNPADDED
-#define CPMPC_FUSED_G_UNPADDED 1
-#endif
+// A column of Gamma_s is an NX-vector: 16 bytes (float, NX = 4), 24 (float, NX = 6), 32 (double, NX = 4) or 48 (double,
+// NX = 6), stored as the pieces it fills at [(i * 64 + lane) * pieces + p].  Round 5 dropped the padding of the 6-state
+// columns to 32 / 64 bytes: Gamma is 30 KB instead of 40 KB per wave for the double 6-state kernel, three waves per CU
+// instead of two (and four with the slim layout above).  Lane-consecutive 16-byte planes, [(i * pieces + p) * 64 + lane],
+// remove the 2-way LDS bank conflicts of the wider columns (SQ_LDS_BANK_CONFLICT 7 800 -> 0 cycles per wave) but were
+// 0.5 % slower (round 4, fp64: 4.832 vs 4.805 ms; profiles/r04_f64_{planes,noplanes}_pmc_summary.json): the lone wave
+// never waited on the conflicts, and the second address per access cost more than they did.
 // A piece is 16 bytes where the column is a whole number of them (float / NX = 4: one; double / NX = 4: two; double /
 // NX = 6: three) and 8 bytes otherwise (float / NX = 6: 24 bytes = three pieces of 8 instead of the padded 32: 15 KB of Gamma
 // per wave instead of 20, which is what lets the float 6-state kernel's LDS fit eight waves per CU, round 5).
@@ -323,14 +243,14 @@ struct alignas(BYTES) GPieceT {
 };
 template <typename R, int NX>
 __host__ __device__ constexpr int fused_g_piece_bytes() {
-  return (CPMPC_FUSED_G_UNPADDED && (NX * sizeof(R)) % 16 != 0) ? 8 : 16;
+  return (NX * sizeof(R)) % 16 != 0 ? 8 : 16;
 }
 template <typename R, int NX>
 using GPieceOf = GPieceT<fused_g_piece_bytes<R, NX>()>;
 template <typename R, int NX>
 __host__ __device__ constexpr int fused_g_pieces() {
   constexpr int PB = fused_g_piece_bytes<R, NX>();
-  return CPMPC_FUSED_G_UNPADDED ? (int)((NX * sizeof(R) + PB - 1) / PB) : (int)(sizeof(XV<R, NX>) / 16);
+  return (int)((NX * sizeof(R) + PB - 1) / PB);
 }
 template <typename R, int NX>
 __host__ __device__ constexpr size_t fused_g_bytes() {  // LDS bytes of one column
@@ -342,7 +262,7 @@ __device__ __forceinline__ XV<R, NX> fused_g_ld(const GPieceOf<R, NX>* g, int i,
   XV<R, NX> v;
   GPieceOf<R, NX> pc[K];
 #pragma unroll
-  for (int p = 0; p < K; ++p) pc[p] = CPMPC_FUSED_G_PLANES ? g[(i * K + p) * 64 + lane] : g[(i * 64 + lane) * K + p];
+  for (int p = 0; p < K; ++p) pc[p] = g[(i * 64 + lane) * K + p];
   __builtin_memcpy(&v, pc, sizeof pc <= sizeof v ? sizeof pc : sizeof v);  // (the padding of v, if any, is never read)
   return v;
 }
@@ -352,50 +272,40 @@ __device__ __forceinline__ void fused_g_st(GPieceOf<R, NX>* g, int i, int lane, 
   GPieceOf<R, NX> pc[K];
   __builtin_memcpy(pc, &v, sizeof pc <= sizeof v ? sizeof pc : sizeof v);
 #pragma unroll
-  for (int p = 0; p < K; ++p) {
-    if (CPMPC_FUSED_G_PLANES) g[(i * K + p) * 64 + lane] = pc[p];
-    else g[(i * 64 + lane) * K + p] = pc[p];
-  }
+  for (int p = 0; p < K; ++p) g[(i * 64 + lane) * K + p] = pc[p];
 }
 
 // SHARED: the batch shares one parameter set -> the model constants stay wave-uniform (scalar registers)
 // REFINE (double kernels only; CPMPC_CREATE_REFINE_QP): one step of iterative refinement of the whole QP solution with
 // residuals from the original data (the block after sweep 2 in mpc_fused_body.inc)
 template <typename R, typename M, int SP, int L, bool SHARED, bool REFINE>
-__global__ CPMPC_FUSED_BOUNDS_S CPMPC_FUSED_EXTRA_ATTR void fused_sqp_kernel(const SolverArgs<R, M> a, const int max_iters) {
+__global__ CPMPC_FUSED_BOUNDS void fused_sqp_kernel(const SolverArgs<R, M> a, const int max_iters) {
   constexpr int NX = M::NX;
   constexpr int PPW = 64 / L;  // problems per wave
   constexpr bool kSlim = fused_slim<R, M, SP, REFINE>();
-  constexpr bool kLean = fused_lean<R, M, SP>() || kSlim;
   __shared__ R lds_u[SP * 64];
   __shared__ R lds_du[SP * 64];
   __shared__ GPieceOf<R, NX> lds_G[SP * 64 * fused_g_pieces<R, NX>()];  // column i of my Gamma_s (fused_g_ld / fused_g_st)
-  __shared__ R lds_gw_own[kLean ? 1 : SP * 64];  // (U^-1 g)_k of my controls
-#ifndef CPMPC_FUSED_ID_REGS
-#define CPMPC_FUSED_ID_REGS 0  // 1: 1/d_k in registers (15 KB of LDS, but the full unroll it needs spills 151 values: slower)
-#endif
-  constexpr bool kIdRegs = (fused_lean<R, M, SP>() && CPMPC_FUSED_ID_REGS) || kSlim;
-  __shared__ R lds_id[kIdRegs ? 1 : SP * 64];      // 1/d_k of my controls
-  R* const lds_gw = kLean ? lds_du : lds_gw_own;
-  R id_reg[kIdRegs ? SP : 1];
-  constexpr int kSweepUnroll = kIdRegs ? SP : CPMPC_SWEEP_UNROLL;  // register-held 1/d_k need static indices: full unroll
-#define CPMPC_ID_SET(I, V)                    \
-  do {                                        \
-    if constexpr (kIdRegs) id_reg[I] = (V);   \
-    else lds_id[(I) * 64 + lane] = (V);       \
+  __shared__ R lds_gw_own[kSlim ? 1 : SP * 64];  // (U^-1 g)_k of my controls
+  __shared__ R lds_id[kSlim ? 1 : SP * 64];      // 1/d_k of my controls
+  R* const lds_gw = kSlim ? lds_du : lds_gw_own;
+  R id_reg[kSlim ? SP : 1];
+  constexpr int kSweepUnroll = kSlim ? SP : kFusedSweepUnroll;  // register-held 1/d_k need static indices: full unroll
+#define CPMPC_ID_SET(I, V)                  \
+  do {                                      \
+    if constexpr (kSlim) id_reg[I] = (V);   \
+    else lds_id[(I) * 64 + lane] = (V);     \
   } while (0)
-#define CPMPC_ID_GET(I) (kIdRegs ? id_reg[kIdRegs ? (I) : 0] : lds_id[kIdRegs ? 0 : (I) * 64 + lane])
+#define CPMPC_ID_GET(I) (kSlim ? id_reg[kSlim ? (I) : 0] : lds_id[kSlim ? 0 : (I) * 64 + lane])
 #define CPMPC_SWEEP_PRAGMA _Pragma("unroll kSweepUnroll")
 // with the sweeps fully unrolled the scheduler hoists all ten controls' LDS reads to the top and spills; a scheduling
 // barrier per control keeps the live ranges those of the rolled loop
-#define CPMPC_SWEEP_FENCE()                                     \
-  do {                                                          \
-    if constexpr (kIdRegs) __builtin_amdgcn_sched_barrier(0);   \
+#define CPMPC_SWEEP_FENCE()                                   \
+  do {                                                        \
+    if constexpr (kSlim) __builtin_amdgcn_sched_barrier(0);   \
   } while (0)
 #define CPMPC_FUSED_MAT2_POW(T, E) mat2_pow<R, (E)>(T)
-#define CPMPC_FUSED_BODY_DYN 0
 #include "mpc_fused_body.inc"
-#undef CPMPC_FUSED_BODY_DYN
 #undef CPMPC_FUSED_MAT2_POW
 #undef CPMPC_SWEEP_PRAGMA
 #undef CPMPC_SWEEP_FENCE
@@ -422,12 +332,10 @@ __global__ CPMPC_FUSED_BOUNDS void fused_sqp_dyn_kernel(const SolverArgs<R, M> a
   R* lds_id = lds_gw + (size_t)SP * 64;
 #define CPMPC_ID_SET(I, V) lds_id[(I) * 64 + lane] = (V)
 #define CPMPC_ID_GET(I) (lds_id[(I) * 64 + lane])
-#define CPMPC_SWEEP_PRAGMA _Pragma("unroll 5")
+#define CPMPC_SWEEP_PRAGMA _Pragma("unroll kFusedSweepUnroll")
 #define CPMPC_SWEEP_FENCE() do { } while (0)
 #define CPMPC_FUSED_MAT2_POW(T, E) mat2_pow_rt<R>(T, (E))
-#define CPMPC_FUSED_BODY_DYN 1
 #include "mpc_fused_body.inc"
-#undef CPMPC_FUSED_BODY_DYN
 #undef CPMPC_FUSED_MAT2_POW
 #undef CPMPC_SWEEP_PRAGMA
 #undef CPMPC_SWEEP_FENCE

@@ -1,15 +1,13 @@
 // mpc_fused_body.inc -- the body of the fused SQP kernel, included by mpc_fused.hpp once with the spacing SP a
 // compile-time constant and the LDS arrays static (the tuned variants), once with SP = a.SP at run time and the same
-// arrays carved from dynamic LDS.  Expects: R, M, L, SHARED, NX, PPW, SP, lds_u, lds_du, lds_G, lds_gw, lds_id (or the lean
+// arrays carved from dynamic LDS.  Expects: R, M, L, SHARED, NX, PPW, SP, lds_u, lds_du, lds_G, lds_gw, lds_id (or the slim
 // layout's CPMPC_ID_SET / CPMPC_ID_GET on registers and lds_gw aliased to lds_du), CPMPC_SWEEP_PRAGMA, a,
 // max_iters in scope and CPMPC_FUSED_MAT2_POW(matrix, exponent) defined; REFINE (bool): the double kernels' full refinement.
   using W = typename WideOf<R>::type;  // the type the terminal Schur complement is carried in (wide.hpp)
-  // column i of my Gamma_s: lds_G is an array of 16-byte (8-byte: float / NX = 6) pieces, piece p of column i at [(i * kGP + p) * 64 + lane], so
-  // that every ds_read_b128 / ds_write_b128 of the wave touches lane-consecutive 16-byte slots (fused_g_ld / fused_g_st)
-  constexpr int kGP = fused_g_pieces<R, NX>();
+  // column i of my Gamma_s: lds_G is an array of 16-byte (8-byte: float / NX = 6) pieces, piece p of column i at
+  // [(i * 64 + lane) * fused_g_pieces + p] (fused_g_ld / fused_g_st)
 #define G_LD(I) (fused_g_ld<R, NX>(lds_G, (I), lane))
 #define G_ST(I, V) (fused_g_st<R, NX>(lds_G, (I), lane, (V)))
-  (void)kGP;
   using WO = Wide<W>;
   constexpr bool kWidened = !std::is_same<W, R>::value;
   // Float kernels, REFINE = true (CPMPC_CREATE_WIDE_QP; round 5; compiled specialisations; default for the 6-state model): everything
@@ -19,10 +17,9 @@
   // at 1.3e-4 median / 3e-3 p99 with S in double and 2.3e-5 / 1.6e-4 with these pieces too; on the GPU the headline's cold
   // starts end 8.4e-5 (median) / 4.9e-3 (p99) from the double check instead of 2.4e-4 / 0.11 -- exactly where the float CPU
   // check ends -- for 2.7 % of the kernel's time; for the 6-state model 4.2e-2 / 8.0 -> 5.7e-4 / 9.3e-3 for 0 - 5 % (HISTORY.md).
-  // -DCPMPC_FUSED_WIDE_QP_F32=1 forces it for every float handle.
-  // (The macro leaves the 4-state model's run-time-spacing kernel out: hipcc 7.2's register allocator crashes on its
-  // SHARED = true instantiation with Q = double; the REFINE instantiation, SHARED = false, compiles.)
-  constexpr bool kWideQP = ((CPMPC_FUSED_WIDE_QP_F32 && (!CPMPC_FUSED_BODY_DYN || NX > 4)) || (REFINE && sizeof(R) == 4)) && kWidened;
+  // (Only the REFINE instantiation carries it: hipcc 7.2's register allocator crashes on the 4-state run-time-spacing
+  // kernel's SHARED = true instantiation with Q = double.)
+  constexpr bool kWideQP = REFINE && kWidened;
   using Q = std::conditional_t<kWideQP, W, R>;
   // one step of iterative refinement of the WHOLE QP solution, residuals from the original data (double kernels; see the
   // block after sweep 2)
@@ -32,15 +29,12 @@
   // w_k = Psi_s wt_k + e_k w_in in a second pass down the block after the boundary chain, instead of as the block-local Gram
   // matrix St of the wt_k in the first pass and the congruence Psi St Psi^T + corrections after it.  Same multiply-adds
   // (84 against 87 per control), but St, Psi St (2 x NX x NX) and the t~, r~, eps, sigma sums never exist: the peak of live
-  // values falls by ~90 doubles.  -DCPMPC_FUSED_TWO_PASS=0 restores the one-pass form (A/B).
-#ifndef CPMPC_FUSED_TWO_PASS
-#define CPMPC_FUSED_TWO_PASS 1
-#endif
+  // values falls by ~90 doubles: 9.7 % of the fp64 kernel time.  The 4-state and full-refinement kernels keep the one pass.
   // structural zeros of Phi and Psi (models.hpp: struct_zero): entries of the columns of a step Jacobian that are known in
   // closed form; SZ(r, c) is false everywhere for a model without such columns (the 4-state one)
-  constexpr unsigned kTriv = CPMPC_JA_TRIVIAL_COLS ? trivial_cols<NX, M::NQ>(JaZeroCols<M>::value) : 0u;
+  constexpr unsigned kTriv = trivial_cols<NX, M::NQ>(JaZeroCols<M>::value);
 #define SZ(r_, c_) (struct_zero<NX, M::NQ>(kTriv, (r_), (c_)))
-  constexpr bool kTwoPass = CPMPC_FUSED_TWO_PASS && NX > 4 && !kFullRefine;
+  constexpr bool kTwoPass = NX > 4 && !kFullRefine;
   CPMPC_TICK_INIT();
   CPMPC_CLOCK_BEGIN();
   const int lane = threadIdx.x;
@@ -92,11 +86,8 @@
   }
   load_terminal<R, M>(a, p, Rw, Dg);
   // which terminal rows are cost rows, as one bit mask instead of NX 0 / 1 values held in registers for the whole launch
-  // (the double 6-state kernel: 12 fewer persistent registers, 173 -> 132 spilled dwords)
-#ifndef CPMPC_FUSED_DG_MASK
-#define CPMPC_FUSED_DG_MASK 1
-#endif
-  constexpr bool kDgMask = CPMPC_FUSED_DG_MASK && NX > 4 && sizeof(R) == 8;
+  // (the double 6-state kernel: 12 fewer persistent registers, 173 -> 132 spilled dwords, 2.5 % of its time)
+  constexpr bool kDgMask = NX > 4 && sizeof(R) == 8;
   int dgm = 0;
   if constexpr (kDgMask) {
 #pragma unroll
@@ -127,8 +118,7 @@
 #pragma unroll
         for (int c = 0; c < NX; ++c) Phi[r][c] = (r == c) ? R(1) : R(0);
       }
-      typename M::StepCache chain;  // what consecutive steps of my interval share (models.hpp)
-      M::chain_begin(chain, x);
+      typename M::StepCache chain;  // what the stages of a step share (models.hpp)
       {
 #pragma unroll 1
         for (int i = 0; i < SP; ++i) {
@@ -165,7 +155,7 @@
             for (int c = 0; c < NX; ++c) Phi[r][c] = T[r][c];
           }
           // Gamma_j <- A Gamma_j for the earlier controls, Gamma_i = B (forward accumulation, in LDS)
-          if constexpr (CPMPC_FUSED_GAMMA_AHEAD(R)) {
+          if constexpr (sizeof(R) == 8) {
             // one column ahead: the read of column j+1 is in flight while column j is multiplied -- with one wave per
             // SIMD, the fp64 case, nothing else covers the LDS round trip of a read that is used at once (with two waves
             // the other one does, and the extra branch and move per column cost fp32 1.5 %)
@@ -603,13 +593,11 @@ CPMPC_SWEEP_PRAGMA
       //     r = (h - rho) - Dg q - sum_k w_k (w_k . q) / d_k
       // evaluated term by term from the columns (never through the rounded S) recovers that: one correction
       // solve with the same factors brings du to 4e-12.  w_k . q = psi . wt_k + e_k (w_in . q) as in sweep 1b.
-      // Kept in fp32 as well (CPMPC_FUSED_REFINE_F32, mpc_fused.hpp): there it is the conditioning of S in single
-      // precision that it repairs (measured: median gap between the fp32 and an fp64 solve 1.7e-3 -> 2.8e-4 for 1 % of the time).
       // Horizons of more than four intervals (L = 8, 16: the states are eliminated through up to 1.6 s of an unstable
       // plant) take a second pass: one lane in a hundred at N = 160 was still 2e-5 from a full-space KKT solve with pivoting.
-      // With the system carried in double inside a float kernel (kWidened) the rounding of S is gone; what the pass
-      // then still repairs is the consistency of q with the float evaluation of W q in sweep 1b (CPMPC_FUSED_REFINE_WIDE).
-      constexpr int kRefinePasses = kWidened ? CPMPC_FUSED_REFINE_WIDE : ((sizeof(R) == 8 || CPMPC_FUSED_REFINE_F32) ? ((sizeof(R) == 8 && L > 4) ? CPMPC_FUSED_REFINE_LONG : 1) : 0);
+      // The float kernels carry the system in double (kWidened, wide.hpp), so the rounding of S the pass repairs is gone
+      // there and they leave it out (round 4: median gap to the fp64 solve 2.44e-4 without it, 2.61e-4 with it).
+      constexpr int kRefinePasses = kWidened ? 0 : (sizeof(R) == 8 && L > 4 ? 2 : 1);
 #pragma unroll 1
       for (int refine = 0; refine < kRefinePasses; ++refine) {
         R psi[NX], wq_in = R(0);
@@ -1051,7 +1039,9 @@ CPMPC_SWEEP_PRAGMA
     // size of the states is taken at the terminal node (target and distance to it) times the number of intervals: group-
     // uniform values every lane holds already (a sum over the nodes cost the double kernel 56 more spilled registers, 1.5 %)
     bool first_order;
-    if constexpr (sizeof(R) == 4 || CPMPC_EXIT_FLOOR_F64) {
+    // The double kernels leave the floor out: at 3e-14 it could change an exit decision only where |D| is within
+    // mu x 3e-14 of the tolerance, and carrying it costs the fp64 fused kernel 1.6 % (4.845 -> 4.925 ms at B = 262 144).
+    if constexpr (sizeof(R) == 4) {
       R x_l1 = R(0);
 #pragma unroll
       for (int t = 0; t < NX; ++t) x_l1 += Math<R>::fabs(tgt[t]) + Math<R>::fabs(e_term[t]);
@@ -1098,7 +1088,6 @@ CPMPC_SWEEP_PRAGMA
       }
       R u_before = (s == 0) ? u_prev : clampr(u_left + alpha * du_left, -a.u_lim, a.u_lim);
       typename M::StepCache chain;
-      M::chain_begin(chain, x);
 #pragma unroll 1
       for (int i = 0; i < SP; ++i) {
         const R u = clampr(lds_u[i * 64 + lane] + alpha * lds_du[i * 64 + lane], -a.u_lim, a.u_lim);

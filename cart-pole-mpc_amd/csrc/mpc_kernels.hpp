@@ -25,13 +25,6 @@
 #include "wide.hpp"
 #include "workspace_layout.hpp"
 
-// threads per workgroup of the one-thread-per-problem kernels before and after the SQP (prepare, finalize)
-#ifndef CPMPC_PF_BLOCK
-#define CPMPC_PF_BLOCK 256
-#endif
-#ifndef CPMPC_EXIT_FLOOR_F64
-#define CPMPC_EXIT_FLOOR_F64 0  // see mpc_fused.hpp
-#endif
 #ifndef CPMPC_SKIP_MERIT
 #define CPMPC_SKIP_MERIT 1      // 0: A/B build that evaluates the merit of a converged step as rounds 1-3 did (NOT the specification)
 #endif
@@ -48,23 +41,9 @@ constexpr int kTermNonFinite = 8;
 
 constexpr int kMaxNX = 6;
 
-// occupancy hints (second argument of __launch_bounds__ = minimum waves per SIMD); 0 = compiler's choice
-#ifndef CPMPC_QPLS_WAVES
-#define CPMPC_QPLS_WAVES 0
-#endif
-#ifndef CPMPC_LIN_WAVES
-#define CPMPC_LIN_WAVES 0
-#endif
-#if CPMPC_QPLS_WAVES > 0
-#define CPMPC_QPLS_BOUNDS __launch_bounds__(64, CPMPC_QPLS_WAVES)
-#else
-#define CPMPC_QPLS_BOUNDS __launch_bounds__(64)
-#endif
-#if CPMPC_LIN_WAVES > 0
-#define CPMPC_LIN_BOUNDS __launch_bounds__(64, CPMPC_LIN_WAVES)
-#else
-#define CPMPC_LIN_BOUNDS __launch_bounds__(64)
-#endif
+// threads per workgroup of the one-thread-per-problem kernels before and after the SQP (prepare, finalize); 256 since
+// round 1 (HISTORY.md, the step to 115.0 M re-plans/s)
+constexpr int kPfBlock = 256;
 
 template <typename R>
 struct VecT;
@@ -279,7 +258,7 @@ __global__ __launch_bounds__(1024) void compact_active_kernel(const int32_t* sta
 }
 
 template <typename R, typename M>
-__global__ __launch_bounds__(CPMPC_PF_BLOCK) void prepare_kernel(const SolverArgs<R, M> a) {  // workgroups as finalize
+__global__ __launch_bounds__(kPfBlock) void prepare_kernel(const SolverArgs<R, M> a) {  // workgroups as finalize
   constexpr int NX = M::NX;
   const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= a.B) return;
@@ -323,7 +302,7 @@ __global__ __launch_bounds__(CPMPC_PF_BLOCK) void prepare_kernel(const SolverArg
   int kk = 0;
   R u_next = guess_u(0);
   for (int s = 1; s < a.S; ++s) {
-    typename M::StepCache chain;  // consecutive steps share the pole angle's sine / cosine base; re-anchored per interval
+    typename M::StepCache chain;  // the stages of a step share the pole angle's sine / cosine base (models.hpp)
     for (int i = 0; i < a.SP; ++i, ++kk) {
       const R u = u_next;
       if (kk + 1 < a.N) u_next = guess_u(kk + 1);
@@ -348,7 +327,7 @@ __global__ __launch_bounds__(CPMPC_PF_BLOCK) void prepare_kernel(const SolverArg
 // equal to the reference's backward accumulation (optimization.cc:145-154).
 // ------------------------------------------------------------------------------------------------
 template <typename R, typename M, int SP>
-__global__ CPMPC_LIN_BOUNDS void linearize_kernel(const SolverArgs<R, M> a, const XV<R, M::NX>* zx_in,
+__global__ __launch_bounds__(64) void linearize_kernel(const SolverArgs<R, M> a, const XV<R, M::NX>* zx_in,
                                                         const R* zu_in, const int32_t* status) {
   constexpr int NX = M::NX;
   const int64_t gid = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -376,7 +355,7 @@ __global__ CPMPC_LIN_BOUNDS void linearize_kernel(const SolverArgs<R, M> a, cons
 
   const R* zu = zu_in + (int64_t)(s * SP) * st;
   R u_next = zu[p];
-  typename M::StepCache chain;  // consecutive steps of the interval share the sine / cosine base (models.hpp)
+  typename M::StepCache chain;  // the stages of a step share the sine / cosine base (models.hpp)
 #pragma unroll 1
   for (int i = 0; i < SP; ++i) {
     const R u = u_next;
@@ -623,7 +602,7 @@ __device__ __forceinline__ void merit_eval(const SolverArgs<R, M>& a, const type
 // in double and leaves y_k in the slot of (U^-1 g)_k.  One more pass over Gamma, Phi and T than the plain kernel: this
 // pipeline is the fall-back for shapes the fused kernel is not built for, correctness is its bar, not throughput.
 template <typename R, typename M, bool WIDEQ = false>
-__global__ CPMPC_QPLS_BOUNDS void qp_ls_kernel(const SolverArgs<R, M> a) {
+__global__ __launch_bounds__(64) void qp_ls_kernel(const SolverArgs<R, M> a) {
   using V4 = typename VecT<R>::V4;
   using XVn = XV<R, M::NX>;
   using W = typename WideOf<R>::type;
@@ -1016,7 +995,7 @@ __global__ CPMPC_QPLS_BOUNDS void qp_ls_kernel(const SolverArgs<R, M> a) {
     // data at the recovered (du, dx), the adjoint walked back through Phi^T; a second solve with the same factors;
     // du, dx and the directional quantities replaced by the corrected ones.  Two more passes over the workspace.
     if constexpr (sizeof(R) == 8 && !kWidened) {
-      // a.refine_qp passes (1: CPMPC_CREATE_REFINE_QP; 3 beyond cpmpc_max_parity_horizon(), round 6): every pass re-evaluates
+      // a.refine_qp passes (1: CPMPC_CREATE_REFINE_QP; 2 beyond cpmpc_max_parity_horizon(), round 6): every pass re-evaluates
       // the residuals at the corrected (du, dx, q) and solves once more with the same factors -- iterative refinement of the
       // KKT system with the condensed solve as the approximate inverse: each pass multiplies a lane's error by that solve's
       // relative error on the lane (1e-3 at worst at 1.6 s), where the condensed solve alone is left with it.
@@ -1190,7 +1169,7 @@ __global__ CPMPC_QPLS_BOUNDS void qp_ls_kernel(const SolverArgs<R, M> a) {
   const R phi0 = f + mu * cn;
   // equality residuals at the rounding floor of the rollout count as zero in the exit test
   bool first_order;
-  if constexpr (sizeof(R) == 4 || CPMPC_EXIT_FLOOR_F64) {   // (the double kernels: see CPMPC_EXIT_FLOOR_F64)
+  if constexpr (sizeof(R) == 4) {   // (the double kernels leave the floor out: see the fused kernel's exit test)
     R x_l1 = R(0);   // the size of the states: target and distance to it at the terminal node, times the number of intervals
 #pragma unroll
     for (int t = 0; t < NX; ++t) x_l1 += Math<R>::fabs(tgt[t]) + Math<R>::fabs(e_term[t]);
@@ -1284,7 +1263,7 @@ __global__ CPMPC_QPLS_BOUNDS void qp_ls_kernel(const SolverArgs<R, M> a) {
 template <typename R, typename M>
 // launched with 256-thread workgroups: 4x fewer workgroups to dispatch for a kernel that is a single round of waves
 // (measured 92 -> 80 us at B = 262 144)
-__global__ __launch_bounds__(CPMPC_PF_BLOCK) void finalize_kernel(const SolverArgs<R, M> a) {
+__global__ __launch_bounds__(kPfBlock) void finalize_kernel(const SolverArgs<R, M> a) {
   constexpr int NX = M::NX;
   const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t st = a.stride;
@@ -1344,7 +1323,7 @@ __global__ __launch_bounds__(CPMPC_PF_BLOCK) void finalize_kernel(const SolverAr
       const R u = u_next;
       if (kk + 1 < a.N) u_next = a.zu[(int64_t)(kk + 1) * st + p];
       if (a.u_out) a.u_out[(int64_t)kk * ob + p] = u;
-      if (kk % 8 == 0) chain.invalidate();  // re-anchor the sine / cosine chain with a full evaluation every 8 steps
+      if (kk % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
       rk4_step_m<R, M, false>(k, a.dt, x, u, fe, chain);
       wrap_angles<R, M>(x);
 #pragma unroll
@@ -1498,7 +1477,7 @@ __global__ __launch_bounds__(64) void sim_kernel(int64_t B, typename M::Consts k
   typename M::StepCache chain;
   for (int i = 0; i < n_sub; ++i) {
     const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-    if (i % 8 == 0) chain.invalidate();  // re-anchor the sine / cosine chain every 8 sub-steps
+    if (i % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
     rk4_step_m<R, M, true>(k, h, xs, uu, fe, chain);
     wrap_angles<R, M>(xs);
   }

@@ -20,14 +20,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
-// 1 (default): the float kernels carry the terminal system in double; 0 builds the A/B variant that keeps it in float
-// (the state of round 3)
-#ifndef CPMPC_WIDE_F32
-#define CPMPC_WIDE_F32 1
-#endif
-
 namespace cpmpc {
 
 template <typename R>
@@ -36,7 +28,7 @@ struct WideOf {
 };
 template <>
 struct WideOf<float> {
-  using type = std::conditional_t<CPMPC_WIDE_F32 != 0, double, float>;
+  using type = double;
 };
 
 template <typename W>
