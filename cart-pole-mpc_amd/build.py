@@ -11,8 +11,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libcpmpc.so")
-# five translation units, compiled in parallel: the C-ABI (no device code) and the kernels of each (dtype, model) pair
-UNITS = ["cpmpc_api", "engine_f32_single", "engine_f64_single", "engine_f32_double", "engine_f64_double"]
+# seven translation units, compiled in parallel: the C-ABI in three (the core, the host-pointer pipeline, the sharded
+# handle; no device code) and the kernels of each (dtype, model) pair
+UNITS = ["cpmpc_api", "cpmpc_host", "cpmpc_sharded", "engine_f32_single", "engine_f64_single", "engine_f32_double",
+         "engine_f64_double"]
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 # -fno-slp-vectorize: on gfx950 a v_pk_fma_f32 issues at ~1.8x the cost of a v_fma_f32 (tools/ubench/pk.hip), so the
 # SLP vectoriser's packing plus its pairing moves is a net loss here (measured 91M -> 104M re-plans/s, 255 -> 189 VGPRs

@@ -1,7 +1,7 @@
-// engine.hpp -- what the C-ABI translation unit (cpmpc_api.hip) and the four kernel translation units
-// (engine_<dtype>_<model>.hip) share: the solver handle, the error / profiling / staging helpers the API owns, and the
+// engine.hpp -- what the C-ABI translation units (cpmpc_api.hip, cpmpc_host.hip, cpmpc_sharded.hip) and the four kernel
+// units (engine_<dtype>_<model>.hip) share: the solver handle, the error / profiling / staging helpers the API owns, and the
 // table of entry points through which the API reaches the kernels of one (dtype, model) pair.  The library is built
-// from five objects compiled in parallel; only the engine units contain device code.
+// from seven objects compiled in parallel; only the engine units contain device code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -116,7 +116,7 @@ struct cpmpc_solver {
 };
 
 
-// owned by the API unit
+// owned by the C-ABI units (cpmpc_api.hip: spans, plan; cpmpc_host.hip: slots, threads)
 CPMPC_HIDDEN void span_begin(cpmpc_solver* s, int kernel, hipStream_t stream, ProfSpan* cur);
 CPMPC_HIDDEN void span_end(cpmpc_solver* s, hipStream_t stream, ProfSpan* cur);
 CPMPC_HIDDEN int ensure_slot(cpmpc_solver* s, int slot, size_t bytes);

@@ -7,7 +7,7 @@ sys.path.insert(0, '.')
 _LIB = os.path.abspath("tools/_build/lib_timing/libcpmpc.so")
 os.environ["CPMPC_LIB"] = _LIB   # before the package is imported: capi fixes its library path at import
 build = importlib.import_module("cart-pole-mpc_amd.build")
-assert build.build_variant("timing", ["-DCPMPC_FUSED_TIMING"]) == _LIB   # the five translation units with the phase counters
+assert build.build_variant("timing", ["-DCPMPC_FUSED_TIMING"]) == _LIB   # the seven translation units with the phase counters
 if "--build-only" in sys.argv:
     sys.exit(0)
 DT = torch.float64 if "f64" in sys.argv else torch.float32
