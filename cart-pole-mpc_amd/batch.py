@@ -267,6 +267,41 @@ class BatchOptimization:
                                                          _ptr(Gam), _stream_ptr()))
         return c, Phi, Gam
 
+    def feedback_gain(self, dyn, n_rows=1, z=None, terminal_weights=None, want_ok=False):
+        """K = du / dx0 of the plan, rows 0 .. n_rows-1: tensor [n_rows, nx, B] with u(x0 + d) ~ u + K d (include/cpmpc.h:
+        cpmpc_feedback_gain_batch).  The gain of the unclamped, undamped QP at z: z None = the handle's previous solution
+        (B = previous_solution_batch()), else a [dim, B] tensor; the warm start is untouched either way.  dyn: np floats
+        (shared) or an [np, B] tensor; terminal_weights: optional [nx, B] tensor as in step().  want_ok: also return the
+        [B] int32 tensor that is 0 for a problem whose QP is not positive definite (its rows are NaN)."""
+        dev = torch.device("cuda", self.device)
+        if z is not None:
+            _require_cuda_tensor(z, "z", self.dtype)
+            if z.dim() != 2 or z.shape[0] != self.dim:
+                raise ValueError("z must be [dim=%d, B]" % self.dim)
+            B = int(z.shape[1])
+        else:
+            B = self.previous_solution_batch()
+            if B < 1:
+                raise ValueError("feedback_gain(z=None) needs a previous solution: step() first, or pass z")
+        n_rows = int(n_rows)
+        inp = capi.GainInputs(struct_size=C.sizeof(capi.GainInputs))
+        if isinstance(dyn, torch.Tensor):
+            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
+            inp.dyn = dyn.data_ptr()
+        else:
+            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
+            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
+        if terminal_weights is not None:
+            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
+            inp.terminal_weights = terminal_weights.data_ptr()
+        inp.z = z.data_ptr() if z is not None else None
+        K = torch.empty((max(n_rows, 0), self.nx, B), dtype=self.dtype, device=dev)
+        ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
+        with torch.cuda.device(self.device):
+            capi.check(capi.load().cpmpc_feedback_gain_batch(self._h, B, C.byref(inp), n_rows, _ptr(K), _ptr(ok),
+                                                             _stream_ptr()))
+        return (K, ok) if want_ok else K
+
     # -- pipeline selection --------------------------------------------------------------------
     def set_pipeline(self, mode):
         """'auto' | 'split' | 'fused' (include/cpmpc.h: CPMPC_PIPELINE_*)."""
@@ -366,6 +401,29 @@ def rk4_batch(dyn, x, u, h, fext=None, jacobians=True, model="single"):
     return (xn, A, Bm) if jacobians else xn
 
 
+def feedback_apply(u_nom, K0, x_nom, x, u_limit=300.0, model="single", out=None):
+    """u [B] = clamp(u_nom + K0 . wrap(x - x_nom), +-u_limit): row 0 of BatchOptimization.feedback_gain() applied to the
+    deviation of the state x [nx, B] from the state x_nom [nx, B] the plan was made for (pole-angle differences wrapped);
+    u_nom [B], K0 [nx, B].  One elementwise launch (cpmpc_feedback_apply_batch)."""
+    m, nx, _ = _model_dims(model)
+    dt = x.dtype
+    _require_cuda_tensor(x, "x", dt)
+    if x.dim() != 2 or x.shape[0] != nx:
+        raise ValueError("x must be [%d, B]" % nx)
+    B = int(x.shape[1])
+    _require_cuda_tensor(x_nom, "x_nom", dt, (nx, B))
+    _require_cuda_tensor(K0, "K0", dt, (nx, B))
+    _require_cuda_tensor(u_nom, "u_nom", dt, (B,))
+    if out is None:
+        out = torch.empty((B,), dtype=dt, device=x.device)
+    else:
+        _require_cuda_tensor(out, "out", dt, (B,))
+    with torch.cuda.device(x.device):
+        capi.check(capi.load().cpmpc_feedback_apply_batch(_CAPI_DTYPE[dt], m, B, _ptr(u_nom), _ptr(K0), _ptr(x_nom),
+                                                          _ptr(x), float(u_limit), _ptr(out), _stream_ptr()))
+    return out
+
+
 class BatchSimulator:
     """B independent pendulum::Simulator plants (optimization/simulator.hpp:10-29)."""
 
@@ -414,7 +472,15 @@ class ClosedLoop:
     (three).  A caller that needs every control of a tick before the next one starts synchronises the streams itself
     (`synchronize()`); the loop as such never does."""
 
-    def __init__(self, params, batch, dtype=torch.float64, device=None, ranges=1, opts=None, model="single", pipeline="auto"):
+    def __init__(self, params, batch, dtype=torch.float64, device=None, ranges=1, opts=None, model="single", pipeline="auto",
+                 feedback=False):
+        """feedback=True: tick() computes the first row K[0] of the feedback gains after every re-plan
+        (BatchOptimization.feedback_gain) and applies u_0 + K[0] . wrap(x - x0) instead of u_0, on the plant's current
+        state in each of tick(substeps=m)'s m plant steps of dt / m: an inner loop m times faster than the re-plan.
+        feedback=False (default): the loop of the reference, unchanged."""
+        self.feedback = bool(feedback)
+        self.model = model
+        self.u_limit = float(opts.u_limit) if opts is not None else float(capi.default_solver_opts().u_limit)
         if device is None:
             device = torch.cuda.current_device()
         self.device = torch.device("cuda", int(device))
@@ -431,6 +497,7 @@ class ClosedLoop:
             self.outs.append(BatchOutputs())
             # one range: the caller's stream, like BatchOptimization alone; several: a stream each
             self.streams.append(torch.cuda.Stream(device=self.device) if ranges > 1 else None)
+        self.applied = [None] * ranges  # feedback=True: per range, the control [n] applied in the last sub-step of the last tick
         self.ticks = 0
         self._inputs_dirty = len(self.sims) > 1   # the plants' initial states were written on the caller's stream
 
@@ -463,8 +530,14 @@ class ClosedLoop:
         st = self.streams[i]
         return torch.cuda.stream(st) if st is not None else torch.cuda.stream(torch.cuda.current_stream(self.device))
 
-    def tick(self, dyn, set_point=0.0, dt=0.01, want_stats=True):
-        """One MPC tick of every controller (queued, not waited for)."""
+    def tick(self, dyn, set_point=0.0, dt=0.01, want_stats=True, substeps=1, fext=None):
+        """One MPC tick of every controller (queued, not waited for).  With feedback=True the plant advances in `substeps`
+        steps of dt / substeps, each under u_0 + K[0] . wrap(x - x0) of its current state; fext: optional callable
+        (range index, sub-step) -> [4, n] tensor of external forces on that range's plants for that sub-step."""
+        if not self.feedback and (int(substeps) != 1 or fext is not None):
+            raise ValueError("ClosedLoop.tick: substeps / fext belong to the feedback loop (ClosedLoop(..., feedback=True))")
+        if int(substeps) < 1:
+            raise ValueError("substeps must be >= 1")
         if isinstance(dyn, torch.Tensor):
             raise TypeError("ClosedLoop.tick: dyn is the plant's parameter set too (cpmpc_sim_step_batch takes shared host "
                             "parameters): pass the %d numbers, not a tensor" % self.sims[0].np)
@@ -484,9 +557,24 @@ class ClosedLoop:
             with self._on(i):
                 # per-problem set-points [B]: this range's columns (copied on the range's stream)
                 sp = set_point if one or not isinstance(set_point, torch.Tensor) else set_point[lo:hi].contiguous()
+                if self.feedback:
+                    self._tick_feedback(i, s, o, out, dyn, sp, dt, want_stats, int(substeps), fext)
+                    continue
                 r = o.step(s.get_state(), dyn, sp, want_predicted=False, want_stats=want_stats, out=out)
                 s.step(dyn, dt, r.u[0].contiguous())
         self.ticks += 1
+
+    def _tick_feedback(self, i, s, o, out, dyn, sp, dt, want_stats, substeps, fext):
+        x0 = s.get_state().clone()  # the state the plan is made for: the plant's own tensor moves under the sub-steps
+        r = o.step(x0, dyn, sp, want_predicted=False, want_stats=want_stats, out=out)
+        K, ok = o.feedback_gain(dyn, n_rows=1, want_ok=True)
+        # a controller whose QP is not positive definite has no gain (NaN rows): it holds the plan's u_0, as the plain loop does
+        K0 = torch.where(ok.bool().unsqueeze(0), K[0], torch.zeros_like(K[0]))
+        u_nom = r.u[0].contiguous()
+        for m in range(substeps):
+            u = feedback_apply(u_nom, K0, x0, s.get_state(), u_limit=self.u_limit, model=self.model)
+            s.step(dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
+        self.applied[i] = u  # the control of the last sub-step
 
     def synchronize(self):
         """Make the caller's stream wait for everything queued on the ranges' streams."""

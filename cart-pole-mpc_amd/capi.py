@@ -44,6 +44,7 @@ SYMBOLS = [
     "cpmpc_sharded_set_previous_solution", "cpmpc_sharded_set_previous_solution_host", "cpmpc_sharded_get_solution",
     "cpmpc_sharded_get_solution_host", "cpmpc_sharded_step_batch_host_in", "cpmpc_sharded_step_batch_ex",
     "cpmpc_step_batch_host_in", "cpmpc_set_host_chunk", "cpmpc_host_register", "cpmpc_host_unregister",
+    "cpmpc_feedback_gain_batch", "cpmpc_feedback_gain_batch_host", "cpmpc_feedback_apply_batch",
 ]
 
 
@@ -164,6 +165,18 @@ class StepHostInputs(C.Structure):
     ]
 
 
+class GainInputs(C.Structure):
+    """cpmpc_gain_inputs: device pointers (cpmpc_feedback_gain_batch) or HOST doubles (..._host); exactly one of
+    dyn_shared_host / dyn; z NULL = the handle's previous solution."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("dyn_shared_host", C.POINTER(C.c_double)),
+        ("dyn", C.c_void_p),
+        ("terminal_weights", C.c_void_p),
+        ("z", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -279,6 +292,9 @@ def load():
     L.cpmpc_set_host_chunk.argtypes = [vp, i64]
     L.cpmpc_host_register.argtypes = [vp, C.c_uint64]
     L.cpmpc_host_unregister.argtypes = [vp]
+    L.cpmpc_feedback_gain_batch.argtypes = [vp, i64, C.POINTER(GainInputs), i32, vp, vp, vp]
+    L.cpmpc_feedback_gain_batch_host.argtypes = [vp, i64, C.POINTER(GainInputs), i32, _dp, _ip]
+    L.cpmpc_feedback_apply_batch.argtypes = [i32, i32, i64, vp, vp, vp, vp, dbl, vp, vp]
     _lib = L
     return L
 

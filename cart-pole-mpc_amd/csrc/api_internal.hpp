@@ -24,6 +24,8 @@ struct DeviceGuard {
 CPMPC_HIDDEN bool device_is_gfx950(int dev);
 // CPMPC_OK, or CPMPC_ERR_NO_DEVICE (with the error text) when the current device is not a usable gfx950
 CPMPC_HIDDEN int current_device_ok();
+// the argument checks of cpmpc_feedback_gain_batch[_host] (no device needed)
+CPMPC_HIDDEN int check_gain_args(const cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* K);
 
 // (cpmpc_host.hip) Grows the device buffer *dev -- and its pinned host mirror *pin when `pin` is given -- to at least
 // `bytes` (*cap: their size); never shrinks, allocates at least 4 096 bytes.  `stream` is synchronised before the old

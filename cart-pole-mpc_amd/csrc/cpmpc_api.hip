@@ -810,6 +810,47 @@ extern "C" int cpmpc_sim_step_batch(int dtype, int64_t B, const double* dyn_shar
                                     stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// feedback gains
+// ------------------------------------------------------------------------------------------------
+int check_gain_args(const cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* K) {
+  if (!s || !in || !K) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  if (in->struct_size != sizeof(cpmpc_gain_inputs))
+    return fail(CPMPC_ERR_INVALID_ARG, "cpmpc_gain_inputs.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_gain_inputs))",
+                (unsigned long long)in->struct_size, sizeof(cpmpc_gain_inputs));
+  if (n_rows < 1 || n_rows > s->N) return fail(CPMPC_ERR_INVALID_ARG, "n_rows must be in [1, window_length = %d]", s->N);
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  if (B > s->cap) return fail(CPMPC_ERR_BATCH, "B=%lld exceeds the capacity %lld given to cpmpc_create", (long long)B, (long long)s->cap);
+  if ((in->dyn_shared_host == nullptr) == (in->dyn == nullptr))
+    return fail(CPMPC_ERR_INVALID_ARG, "exactly one of dyn_shared_host / dyn must be given");
+  if (in->z == nullptr && B > s->prev_B)
+    return fail(CPMPC_ERR_INVALID_ARG, "z is NULL and the handle holds a previous solution for %lld problems only, not %lld",
+                (long long)s->prev_B, (long long)B);
+  return CPMPC_OK;
+}
+
+extern "C" int cpmpc_feedback_gain_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K,
+                                         int32_t* ok, void* stream) {
+  int rc = check_gain_args(s, B, in, n_rows, K);
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  engine_of(s)->feedback_gain(s, B, in, n_rows, K, ok, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  track_caller_stream(s, (hipStream_t)stream);  // the workspace (warm start read, scratch written) was used on the caller's stream
+  return CPMPC_OK;
+}
+
+extern "C" int cpmpc_feedback_apply_batch(int dtype, int model, int64_t B, const void* u_nom, const void* K0,
+                                          const void* x_nom, const void* x, double u_limit, void* u_out, void* stream) {
+  if (!u_nom || !K0 || !x_nom || !x || !u_out) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  if (!(u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no clamp)");
+  int rc = check_piece_args(model, dtype, B);
+  if (rc) return rc;
+  engine_for(dtype, model)->feedback_apply(B, u_nom, K0, x_nom, x, u_limit, u_out, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
+}
+
 // debug builds only (-DCPMPC_FUSED_TIMING / -DCPMPC_FUSED_CLOCK): the counters of fused_sqp_kernel, summed over the
 // kernel translation units (each has its own copies), read and cleared
 static int debug_read_all(int which, unsigned long long* out, int n) {

@@ -335,6 +335,56 @@ extern "C" int cpmpc_get_solution_host(cpmpc_solver* s, int64_t B, double* z_hos
   return get_sol_host_cols(s, B, z_host, B, 0);
 }
 
+// Feedback gains with HOST doubles: one staging slot, [dyn? | terminal_weights? | z? | K | ok] in the handle's dtype, one copy
+// in, the kernels, one copy out, one synchronisation.
+extern "C" int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                                              double* K_host, int32_t* ok_host) {
+  int rc = check_gain_args(s, B, in, n_rows, K_host);
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  const size_t nB = (size_t)B, e = s->esize;
+  const size_t n_dyn = in->dyn ? (size_t)s->NP * nB : 0, n_tw = in->terminal_weights ? (size_t)s->NX * nB : 0;
+  const size_t n_z = in->z ? (size_t)s->dim * nB : 0, n_K = (size_t)n_rows * (size_t)s->NX * nB;
+  const size_t off_K = (n_dyn + n_tw + n_z) * e, off_ok = off_K + n_K * e;
+  rc = ensure_slot(s, 0, off_ok + nB * sizeof(int32_t));
+  if (rc) return rc;
+  HostSlot& sl = s->slot[0];
+  auto to_mirror = [&](const void* src, size_t first, size_t n) {
+    const double* d = (const double*)src;
+    if (s->dtype == CPMPC_F32) {
+      float* h = (float*)sl.pin + first;
+      for (size_t i = 0; i < n; ++i) h[i] = (float)d[i];
+    } else {
+      memcpy((double*)sl.pin + first, d, n * 8);
+    }
+  };
+  if (n_dyn) to_mirror(in->dyn, 0, n_dyn);
+  if (n_tw) to_mirror(in->terminal_weights, n_dyn, n_tw);
+  if (n_z) to_mirror(in->z, n_dyn + n_tw, n_z);
+  if (off_K) HIP_TRY(hipMemcpyAsync(sl.dev, sl.pin, off_K, hipMemcpyHostToDevice, sl.stream));
+  char* d_base = (char*)sl.dev;
+  cpmpc_gain_inputs di = *in;
+  di.dyn = n_dyn ? d_base : nullptr;
+  di.terminal_weights = n_tw ? d_base + n_dyn * e : nullptr;
+  di.z = n_z ? d_base + (n_dyn + n_tw) * e : nullptr;
+  rc = cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_base + off_K, (int32_t*)(d_base + off_ok), sl.stream);
+  hipError_t e1 = hipSuccess;
+  if (rc == CPMPC_OK)
+    e1 = hipMemcpyAsync((char*)sl.pin + off_K, d_base + off_K, n_K * e + nB * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream);
+  const hipError_t e2 = hipStreamSynchronize(sl.stream);  // also on failure: the copy in still reads the pinned mirror
+  if (rc) return rc;
+  if (e1 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e1));
+  if (e2 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e2));
+  if (s->dtype == CPMPC_F32) {
+    const float* h = (const float*)((const char*)sl.pin + off_K);
+    for (size_t i = 0; i < n_K; ++i) K_host[i] = (double)h[i];
+  } else {
+    memcpy(K_host, (const char*)sl.pin + off_K, n_K * 8);
+  }
+  if (ok_host) memcpy(ok_host, (const char*)sl.pin + off_ok, nB * sizeof(int32_t));
+  return CPMPC_OK;
+}
+
 // Staging of the handle-less host-pointer plant step: per host thread and device, grown on demand and kept (a
 // Simulator::Step per 10 ms tick must not allocate; simulator.cc:11-36 has no allocation either).
 struct SimStage {

@@ -202,6 +202,13 @@ struct Engine {
   // debug builds (-DCPMPC_FUSED_TIMING / -DCPMPC_FUSED_CLOCK): read and clear this unit's counters, ADDING them to out
   // (which = 0: eight phase counters, 1: {cycles, 100 MHz ticks, waves, max cycles}); -1 when not built in
   int (*debug_read)(int which, unsigned long long* out);
+  // K = du / dx0 of the QP at z (in->z, or the handle's previous solution): linearisation into the workspace, then
+  // feedback_gain_kernel (feedback_kernels.hpp); K [n_rows][NX][B], ok [B] nullable
+  void (*feedback_gain)(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, int32_t* ok,
+                        hipStream_t stream);
+  // u_out = clamp(u_nom + K0 . wrap(x - x_nom), +-u_limit), elementwise
+  void (*feedback_apply)(int64_t B, const void* u_nom, const void* K0, const void* x_nom, const void* x, double u_limit,
+                         void* u_out, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -9,6 +9,7 @@
 #include "engine.hpp"
 #include "mpc_kernels.hpp"
 #include "mpc_fused.hpp"
+#include "feedback_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -507,6 +508,40 @@ static void sim_impl(int64_t B, const double* dyn_shared_host, const double* fex
                      ext_from_host<R>(fext_host), (const R*)fext, n_sub, (R)h_last, (const R*)u, (R*)state);
 }
 
+// ---- feedback gains ------------------------------------------------------------------------------------------------
+// Linearise at z exactly as linearize_batch_impl does (a caller's z goes through the step buffers dzx / dzu, which hold no
+// state between calls; z == NULL: the warm start itself, read only), then one lane per problem over Phi and Gamma.  The
+// call writes Phi, Gamma, cs, Wk and Tk: scratch that every step recomputes before it reads it.
+template <typename R, typename M>
+static void feedback_gain_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, int32_t* ok,
+                               hipStream_t st) {
+  SolverArgs<R, M> a;
+  fill_args<R, M>(s, B, a);
+  a.dyn = (const R*)in->dyn;
+  a.term_w_pp = (const R*)in->terminal_weights;
+  if (in->dyn == nullptr) a.consts = M::template make<double>(in->dyn_shared_host);
+  const XV<R, M::NX>* zx_in = a.zx;
+  const R* zu_in = a.zu;
+  if (in->z != nullptr) {
+    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->z,
+                       a.dzx, a.dzu);
+    zx_in = a.dzx;
+    zu_in = a.dzu;
+  }
+  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
+  if (sizeof(R) == 4 && s->wide_qp)
+    hipLaunchKernelGGL((feedback_gain_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, ok);
+  else
+    hipLaunchKernelGGL((feedback_gain_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, ok);
+}
+
+template <typename R, typename M>
+static void feedback_apply_impl(int64_t B, const void* u_nom, const void* K0, const void* x_nom, const void* x,
+                                double u_limit, void* u_out, hipStream_t st) {
+  hipLaunchKernelGGL((feedback_apply_kernel<R, M>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, B,
+                     (const R*)u_nom, (const R*)K0, (const R*)x_nom, (const R*)x, (R)u_limit, (R*)u_out);
+}
+
 // debug builds: this unit's copies of the counters (every translation unit has its own __device__ variables)
 static int debug_read_impl(int which, unsigned long long* out) {
 #ifdef CPMPC_FUSED_TIMING
@@ -539,6 +574,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
   const Engine* NAME() {                                                                                             \
     static const Engine e = {&step_batch_impl<R, M>, &host_chunk_begin<R, M>, &host_chunk_end<R, M>, &pack_z_impl<R, M>, \
                              &unpack_z_impl<R, M>,   &dynamics_impl<R, M>,   &rk4_impl<R, M>,      &sim_impl<R, M>,    \
-                             &linearize_batch_impl<R, M>, &debug_read_impl};                                         \
+                             &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
+                             &feedback_apply_impl<R, M>};                                                            \
     return &e;                                                                                                       \
   }

@@ -1,0 +1,282 @@
+// feedback_kernels.hpp -- the feedback gains of the MPC plan, K = du / dx0 (N x NX per problem), and their use between
+// two re-plans.  One problem per lane, no LDS, the workspace layout of mpc_kernels.hpp.
+//
+// The QP of an SQP iteration (qp_ls_kernel, mpc_kernels.hpp) is linear in its initial-state row c_init = z_0 - x0.  With
+// the states eliminated through the shooting recursion, T = U D U^T the tridiagonal control-cost Hessian AT LAMBDA = 0,
+// R = diag(w) M the NX terminal rows (w from load_terminal), W = U^-1 R^T, S = W^T D^-1 W, Dg = 1 on cost rows and 0 on
+// equality rows, and Psi_0 = diag(w) Phi_{S-2} ... Phi_0 (what Psi holds at the end of sweep 1):
+//
+//     K = - U^-T D^-1 W (S + Dg)^-1 Psi_0,         u(x0 + delta) ~ u + K delta.
+//
+// It is the gain of the UNDAMPED, UNCLAMPED QP at the linearisation point z: no +-u_limit / +-b_x_limit retraction, no
+// Levenberg-Marquardt term.  K does not depend on x0, the set-point, u_prev, the residuals or the defects: only on z
+// (through Phi and Gamma, which launch_linearize has left in the workspace), the dynamics parameters, the terminal
+// weights and the two control-cost weights.
+//
+//   sweep 1 (k descending)  as in qp_ls_kernel: upsilon_k, 1 / d_k, w_k = Psi Gamma_k - upsilon_k w_{k+1}, S += w_k w_k^T / d_k,
+//                           Psi <- Psi Phi_s.  Only the rows the caller asked for (k < n_rows) are stored.
+//   LDL^T of S + Dg         in the wide type of wide.hpp, then NX solves: Q = (S + Dg)^-1 Psi_0.
+//   ascending pass          k_row_k = - (w_k . Q) / d_k - upsilon_{k-1} k_row_{k-1}, which stops after n_rows rows.
+// WIDEQ (float handles with cpmpc_wide_qp()): Psi and w_k are carried in double, as in qp_ls_kernel's wide form, and W is
+// never read back in float -- a pass of its own (k descending, NX right-hand sides at once) forms
+//     w_k . Q = psi_s Gamma_k - upsilon_k (w_{k+1} . Q),   psi_s = Phi_{s+1}^T psi_{s+1},   psi_{S-2} = diag(w) Q
+// in double and leaves the rows the caller asked for in the slots of W.
+// The blocks below restate parts of qp_ls_kernel (mpc_kernels.hpp), which must keep its code bit for bit and so cannot share
+// them; a fix there is to be carried over here:
+//   sweep 1            <- "sweep 1 (k descending)": the U D U^T recurrence, m_k / w_k, the lower triangle of S, Psi <- Psi Phi_s
+//                         (without the gradient g, gw, rho, the residuals and the free response; lambda = 0)
+//   LDL^T and solves   <- "(S + Dg) q = h - rho by LDL^T": the factorisation, the pivot test, ldl_solve (NX right-hand sides
+//                         here, no refinement pass)
+//   wide pass          <- "sweep 1b (wide QP only)": psi <- Phi_s^T psi and the w_k . q recurrence, for NX columns at once
+//   ascending pass     <- the du recurrence of "sweep 2": du_k = y_k / d_k - upsilon_{k-1} du_{k-1}, with y = -W Q
+// A lane whose d_k or LDL^T pivot is not positive (or not a number: a poisoned parameter set) reports ok = 0 and gets
+// NaN rows; nothing of a lane depends on its neighbours.
+#pragma once
+#include "mpc_kernels.hpp"
+
+namespace cpmpc {
+
+template <typename R, typename M, bool WIDEQ>
+__global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M> a, const int n_rows, R* __restrict__ K_out,
+                                                            int32_t* __restrict__ ok_out) {
+  using V4 = typename VecT<R>::V4;
+  using XVn = XV<R, M::NX>;
+  using W = typename WideOf<R>::type;
+  using WO = Wide<W>;
+  constexpr bool kWidened = !std::is_same<W, R>::value;
+  constexpr bool kWideQP = WIDEQ && kWidened;
+  using Q = std::conditional_t<kWideQP, W, R>;
+  constexpr int NX = M::NX;
+  const unsigned p = blockIdx.x * 64u + threadIdx.x;
+  if (p >= a.B) return;
+  const int64_t st = a.stride;
+  const int N = a.N, S = a.S, SP = a.SP;
+  const R wu2 = a.wu * a.wu, wd2 = a.wd * a.wd;
+  R Rw[NX], Dg[NX];
+  load_terminal<R, M>(a, p, Rw, Dg);
+
+  // ---- sweep 1 (k descending), lambda = 0 ---------------------------------------------------------
+  W Sm[NX][NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i)
+#pragma unroll
+    for (int j = 0; j < NX; ++j) Sm[i][j] = WO::of(R(0));
+  bool pd_ok = true;
+  Q Psi[NX][NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r)
+#pragma unroll
+    for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
+  {
+    Q wprev[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) wprev[r] = Q(0);
+    R d_next = R(1);
+    const XVn* __restrict__ gam_p = a.Gam + p;
+    XVn G_nx = gam_p[(int64_t)(N - 1) * st];  // software pipeline: column k-1 is loaded before column k is consumed
+    int kk = N - 1;
+    for (int s = S - 2; s >= 0; --s) {
+      for (int i = SP - 1; i >= 0; --i, --kk) {
+        R gk[NX];
+        unpack<R, NX>(G_nx, gk);
+        if (kk > 0) G_nx = gam_p[(int64_t)(kk - 1) * st];
+        // U D U^T recurrence of the tridiagonal control-cost Hessian (off-diagonal -wd2), undamped
+        const R nd = (kk < N - 1 ? R(1) : R(0)) + R(1);  // du rows touching u_k
+        const R diag = wu2 + wd2 * nd;
+        const R ups = (kk < N - 1) ? (-wd2 / d_next) : R(0);
+        const R dk = diag + wd2 * ups;
+        if (!(dk > R(0))) pd_ok = false;
+        const R inv_d = R(1) / dk;
+        d_next = dk;
+        // m_k = Psi Gamma_k ; w_k = m_k - ups w_{k+1}
+        Q wk[NX];
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+          Q m = Psi[r][0] * Q(gk[0]);
+#pragma unroll
+          for (int c = 1; c < NX; ++c) m += Psi[r][c] * Q(gk[c]);
+          wk[r] = m - Q(ups) * wprev[r];
+        }
+        if (kk < n_rows) {  // (wave-uniform) the ascending pass reads these rows only
+          if constexpr (!kWideQP) {
+            R wk_r[NX];
+#pragma unroll
+            for (int r = 0; r < NX; ++r) wk_r[r] = (R)wk[r];
+            a.Wk[(int64_t)kk * st + p] = pack<R, NX>(wk_r);
+          }
+        }
+        if (kWideQP || kk < n_rows) a.Tk[(int64_t)kk * st + p] = mk4<R>(R(0), ups, inv_d, R(0));
+#pragma unroll
+        for (int i2 = 0; i2 < NX; ++i2) {
+          const W wi = (W)wk[i2] * (W)inv_d;
+#pragma unroll
+          for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
+        }
+#pragma unroll
+        for (int r = 0; r < NX; ++r) wprev[r] = wk[r];
+      }
+      // Psi <- Psi Phi_s
+      Q T[NX][NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r)
+#pragma unroll
+        for (int c = 0; c < NX; ++c) T[r][c] = Q(0);
+#pragma unroll
+      for (int m = 0; m < NX; ++m) {
+        R row[NX];
+        unpack<R, NX>(a.Phi[(int64_t)(NX * s + m) * st + p], row);
+#pragma unroll
+        for (int r = 0; r < NX; ++r)
+#pragma unroll
+          for (int c = 0; c < NX; ++c) T[r][c] += Psi[r][m] * Q(row[c]);
+      }
+#pragma unroll
+      for (int r = 0; r < NX; ++r)
+#pragma unroll
+        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+    }
+  }
+
+  // ---- (S + Dg) Q = Psi_0 by LDL^T on the lower triangle, NX right-hand sides ----------------------
+  W Qm[NX][NX];  // Qm[i][j]: row i of the solution for column j of Psi_0
+  {
+    W Lm[NX][NX], dv[NX], idv[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Sm[i][i] += WO::of(Dg[i]);
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      W dj = Sm[j][j];
+#pragma unroll
+      for (int m = 0; m < j; ++m) dj -= Lm[j][m] * Lm[j][m] * dv[m];
+      if (!(dj > W(0))) pd_ok = false;
+      dv[j] = dj;
+      const W inv = wide_inv<R, W>(dj);
+      idv[j] = inv;
+#pragma unroll
+      for (int i = j + 1; i < NX; ++i) {
+        W v = Sm[i][j];
+#pragma unroll
+        for (int m = 0; m < j; ++m) v -= Lm[i][m] * Lm[j][m] * dv[m];
+        Lm[i][j] = v * inv;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      W y[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        W v = (W)Psi[i][j];
+#pragma unroll
+        for (int m = 0; m < i; ++m) v -= Lm[i][m] * y[m];
+        y[i] = v;
+      }
+#pragma unroll
+      for (int i = NX - 1; i >= 0; --i) {
+        W v = y[i] * idv[i];
+#pragma unroll
+        for (int m = i + 1; m < NX; ++m) v -= Lm[m][i] * Qm[m][j];
+        Qm[i][j] = v;
+      }
+    }
+  }
+
+  // ---- wide QP only (k descending): w_k . Q in double, the rows asked for left in the slots of W ---------------------
+  if constexpr (kWideQP) {
+    W psi[NX][NX];  // psi[c][j] = (Psi_s^T Q)[c][j]
+#pragma unroll
+    for (int c = 0; c < NX; ++c)
+#pragma unroll
+      for (int j = 0; j < NX; ++j) psi[c][j] = (W)Rw[c] * Qm[c][j];
+    W om[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) om[j] = W(0);
+    int kk = N - 1;
+    for (int s = S - 2; s >= 0; --s) {
+      for (int i = SP - 1; i >= 0; --i, --kk) {
+        R gk[NX];
+        unpack<R, NX>(a.Gam[(int64_t)kk * st + p], gk);
+        const V4 T = a.Tk[(int64_t)kk * st + p];
+        R wq[NX];
+#pragma unroll
+        for (int j = 0; j < NX; ++j) {
+          W pg = psi[0][j] * (W)gk[0];
+#pragma unroll
+          for (int m = 1; m < NX; ++m) pg += psi[m][j] * (W)gk[m];
+          om[j] = pg - (W)T.y * om[j];
+          wq[j] = (R)om[j];
+        }
+        if (kk < n_rows) a.Wk[(int64_t)kk * st + p] = pack<R, NX>(wq);
+      }
+      if (s == 0) break;
+      // psi <- Phi_s^T psi for the interval below
+      W pn[NX][NX];
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) pn[c][j] = W(0);
+#pragma unroll
+      for (int r = 0; r < NX; ++r) {
+        R row[NX];
+        unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
+#pragma unroll
+        for (int c = 0; c < NX; ++c)
+#pragma unroll
+          for (int j = 0; j < NX; ++j) pn[c][j] += (W)row[c] * psi[r][j];
+      }
+#pragma unroll
+      for (int c = 0; c < NX; ++c)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) psi[c][j] = pn[c][j];
+    }
+  }
+
+  // ---- ascending pass: U^T K = - D^-1 W Q, the first n_rows rows -------------------------------------
+  if (ok_out != nullptr) ok_out[p] = pd_ok ? 1 : 0;
+  const R qnan = R(__builtin_nan(""));
+  W kprev[NX];
+#pragma unroll
+  for (int j = 0; j < NX; ++j) kprev[j] = W(0);
+  W ups_prev = W(0);
+  for (int kk = 0; kk < n_rows; ++kk) {
+    R wr[NX];
+    unpack<R, NX>(a.Wk[(int64_t)kk * st + p], wr);
+    const V4 T = a.Tk[(int64_t)kk * st + p];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      W wq;
+      if constexpr (kWideQP) {
+        wq = (W)wr[j];
+      } else {
+        wq = (W)wr[0] * Qm[0][j];
+#pragma unroll
+        for (int m = 1; m < NX; ++m) wq += (W)wr[m] * Qm[m][j];
+      }
+      const W kr = -(wq * (W)T.z) - ups_prev * kprev[j];
+      kprev[j] = kr;
+      K_out[((int64_t)kk * NX + j) * a.B + p] = pd_ok ? (R)kr : qnan;
+    }
+    ups_prev = (W)T.y;
+  }
+}
+
+// u_out = clamp(u_nom + K0 . wrap(x - x_nom), +-u_limit): the first row of the gains applied to the deviation of the
+// measured state from the state the plan was made for, the pole angles' differences wrapped.  Arrays packed [field][B].
+template <typename R, typename M>
+__global__ __launch_bounds__(256) void feedback_apply_kernel(const int64_t B, const R* __restrict__ u_nom,
+                                                              const R* __restrict__ K0, const R* __restrict__ x_nom,
+                                                              const R* __restrict__ x, const R u_limit,
+                                                              R* __restrict__ u_out) {
+  constexpr int NX = M::NX;
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= B) return;
+  R dx[NX];
+#pragma unroll
+  for (int t = 0; t < NX; ++t) dx[t] = x[t * B + p] - x_nom[t * B + p];
+  wrap_angles<R, M>(dx);
+  R u = u_nom[p];
+#pragma unroll
+  for (int t = 0; t < NX; ++t) u = Math<R>::fma(K0[t * B + p], dx[t], u);
+  u_out[p] = clampr(u, -u_limit, u_limit);
+}
+
+}  // namespace cpmpc

@@ -141,6 +141,12 @@ class Optimization {
   // full-space solve by more than 1e-5 (include/cpmpc.h: cpmpc_horizon_beyond_parity); also in every Step's solver_outputs
   [[nodiscard]] bool HorizonBeyondParity() const noexcept;
 
+  // Feedback gains of the last plan, K = du / dx0: rows 0 .. n_rows-1 (1 <= n_rows <= window_length), row-major
+  // [n_rows][4], for the single controller -- u(x0 + d) ~ u + K d, K[0] the feedback law to apply between two re-plans.
+  // The gain of the unclamped, undamped QP at the previous solution (include/cpmpc.h: cpmpc_feedback_gain_batch); throws
+  // std::invalid_argument before the first Step / SetPreviousSolution or for n_rows out of range.
+  [[nodiscard]] std::vector<double> FeedbackGain(const SingleCartPoleParams& dynamics_params, std::size_t n_rows = 1);
+
   const OptimizationParams& params() const noexcept { return params_; }
 
  private:

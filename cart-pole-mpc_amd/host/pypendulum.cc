@@ -149,6 +149,8 @@ PYBIND11_MODULE(pypendulum, m) {
       .def("set_previous_solution_batch", &Optimization::SetPreviousSolutionBatch, py::arg("z_soa"), py::arg("batch"))
       .def("get_solution_batch", &Optimization::GetSolutionBatch, py::arg("batch"))
       .def("set_host_chunk", &Optimization::SetHostChunk, py::arg("problems"))
+      // K = du / dx0 of the last plan, rows 0 .. n_rows-1 as a flat row-major [n_rows][4] list (Optimization::FeedbackGain)
+      .def("feedback_gain", &Optimization::FeedbackGain, py::arg("dynamics_params"), py::arg("n_rows") = 1)
       // the handle's horizon exceeds cpmpc_max_parity_horizon() (include/cpmpc.h): a per-object status, also in solver_summary()
       .def_property_readonly("horizon_beyond_parity", &Optimization::HorizonBeyondParity);
 

@@ -469,6 +469,47 @@ int cpmpc_sharded_step_batch_ex(cpmpc_sharded* s, int64_t B, const cpmpc_step_in
 int cpmpc_sharded_step_batch(cpmpc_sharded* s, int64_t B, const void* x0, const double* dyn_shared_host,
                              double set_point, const cpmpc_step_outputs* out, void* stream);
 
+/* ---- feedback gains of the plan ----------------------------------------------------------------- */
+/* K = du / dx0: how the planned controls move with the measured state, to first order,
+ *     u(x0 + delta) ~ u + K delta,        K [N][NX] per problem.
+ * The QP an SQP iteration solves is linear in its initial-state row z_0 - x0, so K is one more solve with the factors that
+ * QP builds anyway ("Feedback gains").  K[0] is the time-varying linear feedback law of the real-time-iteration
+ * scheme: it lets a caller run an inner loop faster than the re-plan (cpmpc_feedback_apply_batch), compensate the solve's
+ * latency, or propagate measurement noise through a batch of controllers without re-solving.
+ * What it is NOT: it is the gain of the UNCLAMPED, UNDAMPED QP at the linearisation point z -- no +-u_limit / +-b_x_limit
+ * retraction, Levenberg-Marquardt term 0 whatever damping the last step ended with -- and it knows nothing of a line
+ * search.  It depends on z, the dynamics parameters, the terminal weights and u_cost_weight / u_derivative_cost_weight
+ * only: not on x0, the set-point, u_prev, the residuals or the defects.  Replaces nothing in the reference (which has
+ * one controller and re-plans every tick). */
+typedef struct cpmpc_gain_inputs {
+  uint64_t struct_size;          /* = sizeof(cpmpc_gain_inputs) */
+  const double* dyn_shared_host; /* HOST [NP] parameters shared by the batch, or NULL  } exactly one */
+  const void* dyn;               /* [NP][B] per-problem parameters, or NULL            } of the two  */
+  const void* terminal_weights;  /* [NX][B] per-problem terminal weights (cpmpc_step_inputs), or NULL: the handle's */
+  const void* z;                 /* [dim][B] linearisation point (MapKey order), or NULL: the handle's previous solution --
+                                  * the un-shifted z of the last step, what cpmpc_get_solution returns -- which must cover
+                                  * B (cpmpc_previous_solution_batch), else CPMPC_ERR_INVALID_ARG.  A z given here goes through
+                                  * the step buffers like cpmpc_linearize_batch's: the warm start is untouched either way */
+} cpmpc_gain_inputs;
+/* K [n_rows][NX][B] (batch fastest, the handle's dtype), rows 0 .. n_rows-1 of the gain, 1 <= n_rows <= N; row 0 alone
+ * costs one linearisation and one pass over it.  ok [B], nullable: 1, or 0 for a problem whose control-cost pivots or
+ * terminal system are not positive definite (or not numbers: a poisoned parameter set) -- its rows are NaN, its
+ * neighbours are not affected.  Float handles carry the NX x NX terminal system in double; with cpmpc_wide_qp() the
+ * products of transition matrices and the columns of U^-1 R^T as well.  Asynchronous on `stream`; writes only scratch of
+ * the workspace that every step recomputes (a step's results do not depend on gain calls made in between). */
+int cpmpc_feedback_gain_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K,
+                              int32_t* ok /*nullable*/, void* stream);
+/* The same with HOST doubles (every pointer of `in`, K_host [n_rows][NX][B], ok_host [B] nullable); synchronous.  Used by
+ * the C++ facade (pendulum::Optimization::FeedbackGain). */
+int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, double* K_host,
+                                   int32_t* ok_host /*nullable*/);
+/* u_out [B] = clamp(u_nom + K0 . wrap(x - x_nom), +-u_limit): the first row of the gains (K0 [NX][B]) applied to the
+ * deviation of the state x [NX][B] from the state x_nom [NX][B] the plan was made for, the differences of the pole angles
+ * wrapped to (-pi, pi]; u_nom [B].  u_limit > 0 (infinity: no clamp).  One elementwise launch, asynchronous on `stream`;
+ * u_out may alias u_nom. */
+int cpmpc_feedback_apply_batch(int dtype, int model, int64_t B, const void* u_nom, const void* K0, const void* x_nom,
+                               const void* x, double u_limit, void* u_out, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 enum {
