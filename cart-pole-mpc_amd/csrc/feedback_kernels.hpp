@@ -21,14 +21,12 @@
 // never read back in float -- a pass of its own (k descending, NX right-hand sides at once) forms
 //     w_k . Q = psi_s Gamma_k - upsilon_k (w_{k+1} . Q),   psi_s = Phi_{s+1}^T psi_{s+1},   psi_{S-2} = diag(w) Q
 // in double and leaves the rows the caller asked for in the slots of W.
-// The blocks below restate parts of qp_ls_kernel (mpc_kernels.hpp), which must keep its code bit for bit and so cannot share
-// them; a fix there is to be carried over here:
-//   sweep 1            <- "sweep 1 (k descending)": the U D U^T recurrence, m_k / w_k, the lower triangle of S, Psi <- Psi Phi_s
-//                         (without the gradient g, gw, rho, the residuals and the free response; lambda = 0)
-//   LDL^T and solves   <- "(S + Dg) q = h - rho by LDL^T": the factorisation, the pivot test, ldl_solve (NX right-hand sides
-//                         here, no refinement pass)
-//   wide pass          <- "sweep 1b (wide QP only)": psi <- Phi_s^T psi and the w_k . q recurrence, for NX columns at once
-//   ascending pass     <- the du recurrence of "sweep 2": du_k = y_k / d_k - upsilon_{k-1} du_{k-1}, with y = -W Q
+// The pivot step of sweep 1, the LDL^T with its solves and the adjoint product psi <- Phi_s^T psi are the blocks of
+// condensed_qp.hpp that qp_ls_kernel is made of too.  The rest of sweep 1 below still restates "sweep 1 (k descending)" of
+// qp_ls_kernel (without the gradient g, gw, rho, the residuals and the free response): tried one at a time in that kernel,
+// the rank-one update of S as a shared function cost its float instantiations a wave per SIMD (4 states 166 -> 170 VGPRs,
+// 3 -> 2 waves; 6 states 256 -> 256 + 96 AGPRs, 2 -> 1) and Psi <- Psi Phi_s the 6-state one (256 -> 256 + 14, 2 -> 1), with
+// no arithmetic opcode changed; they stay in place in both kernels, and a fix there is to be carried over here.
 // A lane whose d_k or LDL^T pivot is not positive (or not a number: a poisoned parameter set) reports ok = 0 and gets
 // NaN rows; nothing of a lane depends on its neighbours.
 #pragma once
@@ -68,9 +66,9 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
 #pragma unroll
     for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
   {
-    Q wprev[NX];
+    Q wk[NX];  // w_{k+1}, then w_k
 #pragma unroll
-    for (int r = 0; r < NX; ++r) wprev[r] = Q(0);
+    for (int r = 0; r < NX; ++r) wk[r] = Q(0);
     R d_next = R(1);
     const XVn* __restrict__ gam_p = a.Gam + p;
     XVn G_nx = gam_p[(int64_t)(N - 1) * st];  // software pipeline: column k-1 is loaded before column k is consumed
@@ -81,22 +79,13 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
         unpack<R, NX>(G_nx, gk);
         if (kk > 0) G_nx = gam_p[(int64_t)(kk - 1) * st];
         // U D U^T recurrence of the tridiagonal control-cost Hessian (off-diagonal -wd2), undamped
-        const R nd = (kk < N - 1 ? R(1) : R(0)) + R(1);  // du rows touching u_k
-        const R diag = wu2 + wd2 * nd;
-        const R ups = (kk < N - 1) ? (-wd2 / d_next) : R(0);
-        const R dk = diag + wd2 * ups;
+        R ups, dk, inv_d;
+        tridiag_pivot(kk, N, wu2, wd2, R(0), d_next, ups, dk, inv_d);
         if (!(dk > R(0))) pd_ok = false;
-        const R inv_d = R(1) / dk;
         d_next = dk;
         // m_k = Psi Gamma_k ; w_k = m_k - ups w_{k+1}
-        Q wk[NX];
 #pragma unroll
-        for (int r = 0; r < NX; ++r) {
-          Q m = Psi[r][0] * Q(gk[0]);
-#pragma unroll
-          for (int c = 1; c < NX; ++c) m += Psi[r][c] * Q(gk[c]);
-          wk[r] = m - Q(ups) * wprev[r];
-        }
+        for (int r = 0; r < NX; ++r) wk[r] = dot<Q>(Psi[r], gk) - Q(ups) * wk[r];
         if (kk < n_rows) {  // (wave-uniform) the ascending pass reads these rows only
           if constexpr (!kWideQP) {
             R wk_r[NX];
@@ -112,8 +101,6 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
 #pragma unroll
           for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
         }
-#pragma unroll
-        for (int r = 0; r < NX; ++r) wprev[r] = wk[r];
       }
       // Psi <- Psi Phi_s
       Q T[NX][NX];
@@ -138,45 +125,18 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
   }
 
   // ---- (S + Dg) Q = Psi_0 by LDL^T on the lower triangle, NX right-hand sides ----------------------
-  W Qm[NX][NX];  // Qm[i][j]: row i of the solution for column j of Psi_0
+  W Qm[NX][NX];  // Qm[j]: the solution for column j of Psi_0
   {
-    W Lm[NX][NX], dv[NX], idv[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) Sm[i][i] += WO::of(Dg[i]);
+    TerminalLDL<R, NX> ldl;
+    if (!ldl.factor(Sm)) pd_ok = false;
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
-      W dj = Sm[j][j];
+      W b[NX];
 #pragma unroll
-      for (int m = 0; m < j; ++m) dj -= Lm[j][m] * Lm[j][m] * dv[m];
-      if (!(dj > W(0))) pd_ok = false;
-      dv[j] = dj;
-      const W inv = wide_inv<R, W>(dj);
-      idv[j] = inv;
-#pragma unroll
-      for (int i = j + 1; i < NX; ++i) {
-        W v = Sm[i][j];
-#pragma unroll
-        for (int m = 0; m < j; ++m) v -= Lm[i][m] * Lm[j][m] * dv[m];
-        Lm[i][j] = v * inv;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      W y[NX];
-#pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        W v = (W)Psi[i][j];
-#pragma unroll
-        for (int m = 0; m < i; ++m) v -= Lm[i][m] * y[m];
-        y[i] = v;
-      }
-#pragma unroll
-      for (int i = NX - 1; i >= 0; --i) {
-        W v = y[i] * idv[i];
-#pragma unroll
-        for (int m = i + 1; m < NX; ++m) v -= Lm[m][i] * Qm[m][j];
-        Qm[i][j] = v;
-      }
+      for (int i = 0; i < NX; ++i) b[i] = (W)Psi[i][j];
+      ldl.solve(b, Qm[j]);
     }
   }
 
@@ -186,7 +146,7 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
 #pragma unroll
     for (int c = 0; c < NX; ++c)
 #pragma unroll
-      for (int j = 0; j < NX; ++j) psi[c][j] = (W)Rw[c] * Qm[c][j];
+      for (int j = 0; j < NX; ++j) psi[c][j] = (W)Rw[c] * Qm[j][c];
     W om[NX];
 #pragma unroll
     for (int j = 0; j < NX; ++j) om[j] = W(0);
@@ -208,25 +168,7 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
         if (kk < n_rows) a.Wk[(int64_t)kk * st + p] = pack<R, NX>(wq);
       }
       if (s == 0) break;
-      // psi <- Phi_s^T psi for the interval below
-      W pn[NX][NX];
-#pragma unroll
-      for (int c = 0; c < NX; ++c)
-#pragma unroll
-        for (int j = 0; j < NX; ++j) pn[c][j] = W(0);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
-#pragma unroll
-        for (int c = 0; c < NX; ++c)
-#pragma unroll
-          for (int j = 0; j < NX; ++j) pn[c][j] += (W)row[c] * psi[r][j];
-      }
-#pragma unroll
-      for (int c = 0; c < NX; ++c)
-#pragma unroll
-        for (int j = 0; j < NX; ++j) psi[c][j] = pn[c][j];
+      phi_transpose_times(a.Phi, s, st, p, psi);  // for the interval below
     }
   }
 
@@ -244,13 +186,8 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
       W wq;
-      if constexpr (kWideQP) {
-        wq = (W)wr[j];
-      } else {
-        wq = (W)wr[0] * Qm[0][j];
-#pragma unroll
-        for (int m = 1; m < NX; ++m) wq += (W)wr[m] * Qm[m][j];
-      }
+      if constexpr (kWideQP) wq = (W)wr[j];
+      else wq = dot<W>(wr, Qm[j]);
       const W kr = -(wq * (W)T.z) - ups_prev * kprev[j];
       kprev[j] = kr;
       K_out[((int64_t)kk * NX + j) * a.B + p] = pd_ok ? (R)kr : qnan;

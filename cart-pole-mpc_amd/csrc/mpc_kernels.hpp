@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "condensed_qp.hpp"
 #include "models.hpp"
 #include "wide.hpp"
 #include "workspace_layout.hpp"
@@ -44,52 +45,6 @@ constexpr int kMaxNX = 6;
 // threads per workgroup of the one-thread-per-problem kernels before and after the SQP (prepare, finalize); 256 since
 // round 1 (HISTORY.md, the step to 115.0 M re-plans/s)
 constexpr int kPfBlock = 256;
-
-template <typename R>
-struct VecT;
-template <>
-struct VecT<float> {
-  using V4 = float4;
-};
-template <>
-struct VecT<double> {
-  using V4 = double4;
-};
-
-template <typename R>
-__device__ __forceinline__ typename VecT<R>::V4 mk4(R a, R b, R c, R d) {
-  typename VecT<R>::V4 v;
-  v.x = a;
-  v.y = b;
-  v.z = c;
-  v.w = d;
-  return v;
-}
-
-// storage element of an NX-vector: ceil(NX/4) 4-vectors
-template <typename R, int NX>
-struct XV {
-  typename VecT<R>::V4 v[(NX + 3) / 4];
-};
-
-template <typename R, int NX>
-__device__ __forceinline__ void unpack(const XV<R, NX>& s, R (&x)[NX]) {
-  x[0] = s.v[0].x;
-  x[1] = s.v[0].y;
-  x[2] = s.v[0].z;
-  x[3] = s.v[0].w;
-  if constexpr (NX > 4) {
-    x[4] = s.v[1].x;
-    x[5] = s.v[1].y;
-  }
-}
-template <typename R, int NX>
-__device__ __forceinline__ XV<R, NX> pack(const R (&x)[NX]) {
-  XV<R, NX> s;
-  s.v[0] = mk4<R>(x[0], x[1], x[2], x[3]);
-  if constexpr (NX > 4) s.v[1] = mk4<R>(x[4], x[5], R(0), R(0));
-  return s;
-}
 
 template <typename R, typename M>
 struct SolverArgs {
@@ -200,13 +155,6 @@ __device__ __forceinline__ R clampr(R v, R lo, R hi) {
 template <typename R>
 __device__ __forceinline__ R nan_max(R a, R b) {
   return (sizeof(R) == 8) ? (R)__builtin_fmax((double)a, (double)b) : (R)__builtin_fmaxf((float)a, (float)b);
-}
-
-// reciprocal of a pivot of the terminal system in its wide type W; W == R keeps the kernel's own division
-template <typename R, typename W>
-__device__ __forceinline__ W wide_inv(const W d) {
-  if constexpr (std::is_same<W, R>::value) return Math<R>::div(R(1), d);
-  else return Math<double>::div(1.0, d);
 }
 
 // wrap the pole angles of a state / state difference
@@ -575,580 +523,158 @@ __device__ __forceinline__ void merit_eval(const SolverArgs<R, M>& a, const type
   cn_out = cn;
 }
 
-// ------------------------------------------------------------------------------------------------
-// qp_ls: one thread per problem.  Solves
-//     min 1/2 |J dz + r|^2 + 1/2 lambda |du|^2   s.t.  A dz + c = 0
-// exactly, without forming it: the states are eliminated through the shooting recursion
-//     dx_0 = -c_init,  dx_{s+1} = Phi_s dx_s + Gamma_s du_s + c_s,
-// which leaves a QP in du whose Hessian is T + R^T R with T tridiagonal (control costs) and R the
-// <= NX terminal rows (cost or equality).
-//   sweep 1 (k descending): T = U D U^T by a scalar recurrence; W = U^-1 R^T row by row from
-//           m_k = Psi Gamma_k, Psi = diag(w) Phi_{S-2} ... Phi_{s+1}; gw = U^-1 g; accumulate
-//           S = W^T D^-1 W (NX x NX), rho = W^T D^-1 gw and the weighted free response sum_s Psi_s c_s;
-//           rows of W and {gw, upsilon, 1/d, g} are stored.
-//   NX x NX LDL^T of S + diag(1 for cost rows, 0 for equality rows) in registers -> multipliers q.
-//   sweep 2 (k ascending): y = -(gw + W q), U^T du = D^-1 y, state recovery through Phi/Gamma, and the
-//           directional quantities g.du and |J dz|^2.
-// Then the l1-merit penalty update and the Armijo line search with quadratic-interpolation
-// backtracking, started from the remembered step length.
-// ------------------------------------------------------------------------------------------------
-// The terminal system (S, rho, the weighted free response, the LDL^T and its solve) is carried in the wide type W of
-// wide.hpp: double in a float kernel, R itself in a double kernel.
-// WIDEQ (float handles with CPMPC_CREATE_WIDE_QP, the default for the 6-state model; round 6): as in the fused kernel (type Q
-// of mpc_fused_body.inc), everything between the linearisation and the multipliers' effect on the step is carried in double
-// too -- the Psi products across the intervals, the columns w_k of U^-1 R^T, psi = Psi^T q and y = -(gw + W q).  W is then
-// never read back in float: after the multipliers are known a pass of its own ("sweep 1b", k descending) forms
-//     w_k . q = psi_s . Gamma_k - ups_k (w_{k+1} . q),   psi_s = Phi_{s+1}^T psi_{s+1},  psi_{S-2} = diag(w) q
-// in double and leaves y_k in the slot of (U^-1 g)_k.  One more pass over Gamma, Phi and T than the plain kernel: this
-// pipeline is the fall-back for shapes the fused kernel is not built for, correctness is its bar, not throughput.
-template <typename R, typename M, bool WIDEQ = false>
-__global__ __launch_bounds__(64) void qp_ls_kernel(const SolverArgs<R, M> a) {
-  using V4 = typename VecT<R>::V4;
-  using XVn = XV<R, M::NX>;
-  using W = typename WideOf<R>::type;
-  using WO = Wide<W>;
-  constexpr bool kWidened = !std::is_same<W, R>::value;
-  constexpr bool kWideQP = WIDEQ && kWidened;
-  using Q = std::conditional_t<kWideQP, W, R>;
-  constexpr int NX = M::NX;
-  const unsigned p = blockIdx.x * 64u + threadIdx.x;
-  if (p >= a.B) return;
-  const int64_t st = a.stride;
-  if (a.ist[IS_STATUS * st + p] != kTermNone) return;
-  const typename M::Consts k = load_consts(a, p);
-  const int N = a.N, S = a.S, SP = a.SP;
-
-  R lam = a.sc[SC_LAMBDA * st + p];
-  R mu = a.sc[SC_MU * st + p];
-  const R u_prev = a.sc[SC_UPREV * st + p];
-  R a_start = a.sc[SC_ALPHA * st + p];
-  R tgt[NX], xm[NX];
+// g . du and |J dz|^2 of the terminal cost rows at the recovered last node
+template <typename R, int NX>
+__device__ __forceinline__ void terminal_directional(const R (&Rw)[NX], const R (&Dg)[NX], const R (&e_term)[NX],
+                                                     const R (&dx)[NX], R& gd, R& curv) {
 #pragma unroll
   for (int t = 0; t < NX; ++t) {
-    tgt[t] = a.term_tgt[t];
-    xm[t] = a.x0[t * a.B + p];
-  }
-  if (a.set_point) tgt[0] = a.set_point[p];
-
-  const R wu2 = a.wu * a.wu, wd2 = a.wd * a.wd;
-
-  // ---- residuals at z: initial-state rows, terminal rows -----------------------------------------
-  R f = R(0), cn = R(0);
-  R ci[NX];
-  {
-    R z0[NX];
-    unpack<R, NX>(a.zx[p], z0);
-#pragma unroll
-    for (int t = 0; t < NX; ++t) ci[t] = z0[t] - xm[t];
-    wrap_angles<R, M>(ci);
-#pragma unroll
-    for (int t = 0; t < NX; ++t) cn += Math<R>::fabs(ci[t]);
-  }
-  // The weighted free response  ha = diag(w) dx_{S-1}|_{du=0} = sum_s Psi_s c_s - Psi_{-1} c_init  is
-  // accumulated inside sweep 1, where Psi_s = diag(w) Phi_{S-2}...Phi_{s+1} is available anyway.
-  W hv[NX];
-  R Rw[NX], Dg[NX], e_term[NX];
-  {
-    R zt[NX];
-    unpack<R, NX>(a.zx[(int64_t)(S - 1) * st + p], zt);
-#pragma unroll
-    for (int t = 0; t < NX; ++t) e_term[t] = zt[t] - tgt[t];
-    wrap_angles<R, M>(e_term);
-    load_terminal<R, M>(a, p, Rw, Dg);
-#pragma unroll
-    for (int t = 0; t < NX; ++t) {
-      const bool is_cost = Dg[t] != R(0);
-      if (is_cost) {
-        const R r = Rw[t] * e_term[t];
-        f += r * r;
-      } else {
-        cn += Math<R>::fabs(e_term[t]);
-      }
-      hv[t] = WO::prod(Rw[t], e_term[t]);  // + ha[t], added after sweep 1
+    if (Dg[t] != R(0)) {
+      const R jd = Rw[t] * dx[t];
+      gd += (Rw[t] * e_term[t]) * jd;
+      curv += jd * jd;
     }
   }
+}
 
-  // ---- sweep 1 (k descending) -------------------------------------------------------------------
-  W Sm[NX][NX], rho[NX];
+// One step of iterative refinement of the whole QP solution (CPMPC_CREATE_REFINE_QP; mpc_fused_body.inc, where the fused
+// kernel does the same after its sweep 2, says why), phase 6 of qp_ls_kernel, double kernels only: residuals of the terminal rows and of stationarity in the ORIGINAL
+// data at the recovered (du, dx), the adjoint walked back through Phi^T; a second solve with the same factors; du, dx, the
+// multipliers q and the directional quantities replaced by the corrected ones.  Two more passes over the workspace.
+// Iterative refinement of the KKT system with the condensed solve as the approximate inverse: each pass multiplies a
+// lane's error by that solve's relative error on the lane (1e-3 at worst at 1.6 s), where the condensed solve alone is
+// left with it.
+template <typename R, typename M>
+__device__ __forceinline__ void refine_qp_pass(const SolverArgs<R, M>& a, const unsigned p, const R wu2, const R wd2,
+                                               const R lam, const R u_prev,
+                                               const R (&Rw)[M::NX], const R (&Dg)[M::NX], const R (&e_term)[M::NX],
+                                               const R (&ci)[M::NX], const TerminalLDL<R, M::NX>& ldl, R (&q)[M::NX],
+                                               R (&dx)[M::NX], R& gd, R& curv, R& dz_inf) {
+  using V4 = typename VecT<R>::V4;
+  constexpr int NX = M::NX;
+  const int64_t st = a.stride;
+  const int N = a.N, S = a.S, SP = a.SP;
+  R viol[NX], lamv[NX];
 #pragma unroll
-  for (int i = 0; i < NX; ++i) {
-    rho[i] = WO::of(R(0));
-#pragma unroll
-    for (int j = 0; j < NX; ++j) Sm[i][j] = WO::of(R(0));
+  for (int t = 0; t < NX; ++t) {
+    const R rT = Rw[t] * (dx[t] + e_term[t]);
+    const bool cost = Dg[t] != R(0);
+    lamv[t] = Rw[t] * (cost ? rT : q[t]);  // the adjoint at the terminal node, diag(Rw) mult
+    viol[t] = cost ? R(0) : rT;
   }
-  bool pd_ok = true;
-  {
-    Q Psi[NX][NX];
+  R rho2[NX];
 #pragma unroll
-    for (int r = 0; r < NX; ++r)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
-    Q wprev[NX];
-    W ha[NX];
-#pragma unroll
-    for (int r = 0; r < NX; ++r) {
-      wprev[r] = Q(0);
-      ha[r] = WO::of(R(0));
-    }
-    R gwprev = R(0);
-    R d_next = R(1);
-    const XVn* __restrict__ gam_p = a.Gam + p;
-    const R* __restrict__ zu_p = a.zu + p;
-    R u_hi = R(0);                              // u_{k+1}
-    R u_cur = zu_p[(int64_t)(N - 1) * st];      // u_k
-    // software pipeline: the loads of column k-1 are issued before column k is consumed
-    XVn G_nx = gam_p[(int64_t)(N - 1) * st];
-    R u_nx = (N > 1) ? zu_p[(int64_t)(N - 2) * st] : u_prev;
-    int kk = N - 1;
+  for (int t = 0; t < NX; ++t) rho2[t] = R(0);
+  {  // descending: rstat_k = (T du)_k + g_k + Gamma_k . lambda_s, gw'_k = rstat_k - ups_k gw'_{k+1}, rho' += w_k gw'_k / d_k
+    R gw_next = R(0);
+    R du_hi = R(0), du_cur = a.dzu[(int64_t)(N - 1) * st + p];
+    R u_hi = R(0), u_cur = a.zu[(int64_t)(N - 1) * st + p];
+    int k2 = N - 1;
     for (int s = S - 2; s >= 0; --s) {
-      for (int i = SP - 1; i >= 0; --i, --kk) {
-        R gk[NX];
-        unpack<R, NX>(G_nx, gk);
-        const R u_lo = u_nx;  // u_{k-1} (u_prev for k = 0)
-        if (kk > 0) {
-          G_nx = gam_p[(int64_t)(kk - 1) * st];
-          u_nx = (kk > 1) ? zu_p[(int64_t)(kk - 2) * st] : u_prev;
-        }
-        // control cost rows at z, tridiagonal entries and the control-cost gradient g_k
-        const R ru = a.wu * u_cur, rd = a.wd * (u_lo - u_cur);
-        f += ru * ru + rd * rd;
-        const R nd = (kk < N - 1 ? R(1) : R(0)) + R(1);  // du rows touching u_k
-        const R diag = wu2 + lam + wd2 * nd;
+      for (int i = SP - 1; i >= 0; --i, --k2) {
+        const bool inner = k2 < N - 1;
+        const R du_lo = (k2 > 0) ? a.dzu[(int64_t)(k2 - 1) * st + p] : R(0);
+        const R u_lo = (k2 > 0) ? a.zu[(int64_t)(k2 - 1) * st + p] : u_prev;
         R g = wu2 * u_cur + wd2 * (u_cur - u_lo);
-        if (kk < N - 1) g += wd2 * (u_cur - u_hi);
-        // U D U^T recurrence (off-diagonal of T is -wd2)
-        const R ups = (kk < N - 1) ? (-wd2 / d_next) : R(0);
-        const R dk = diag + wd2 * ups;
-        if (!(dk > R(0))) pd_ok = false;
-        const R inv_d = R(1) / dk;
-        d_next = dk;
-        // m_k = Psi Gamma_k ; w_k = m_k - ups w_{k+1}
-        Q wk[NX];
+        if (inner) g += wd2 * (u_cur - u_hi);
+        R G[NX], Wr[NX];
+        unpack<R, NX>(a.Gam[(int64_t)k2 * st + p], G);
+        unpack<R, NX>(a.Wk[(int64_t)k2 * st + p], Wr);
+        V4 T = a.Tk[(int64_t)k2 * st + p];
+        R rstat = (wu2 + lam + wd2 * ((inner ? R(1) : R(0)) + R(1))) * du_cur - wd2 * du_lo + g;
+        if (inner) rstat -= wd2 * du_hi;
 #pragma unroll
-        for (int r = 0; r < NX; ++r) {
-          Q m = Psi[r][0] * Q(gk[0]);
+        for (int m = 0; m < NX; ++m) rstat += G[m] * lamv[m];
+        const R gw2 = rstat - T.y * gw_next;
+        const R t2 = gw2 * T.z;
 #pragma unroll
-          for (int c = 1; c < NX; ++c) m += Psi[r][c] * Q(gk[c]);
-          wk[r] = m - Q(ups) * wprev[r];
-        }
-        const R gw = g - ups * gwprev;
-        if constexpr (!kWideQP) {  // (the wide kernel never reads W back: sweep 1b below)
-          R wk_r[NX];
-#pragma unroll
-          for (int r = 0; r < NX; ++r) wk_r[r] = (R)wk[r];
-          a.Wk[(int64_t)kk * st + p] = pack<R, NX>(wk_r);
-        }
-        a.Tk[(int64_t)kk * st + p] = mk4<R>(gw, ups, inv_d, g);
-#pragma unroll
-        for (int i2 = 0; i2 < NX; ++i2) {
-          const W wi = (W)wk[i2] * (W)inv_d;  // exact in W for float columns: S is the Gram matrix of the rounded rows (wide.hpp)
-          rho[i2] += wi * gw;
-#pragma unroll
-          for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
-        }
-#pragma unroll
-        for (int r = 0; r < NX; ++r) wprev[r] = wk[r];
-        gwprev = gw;
+        for (int m = 0; m < NX; ++m) rho2[m] += Wr[m] * t2;
+        T.x = gw2;
+        a.Tk[(int64_t)k2 * st + p] = T;
+        gw_next = gw2;
+        du_hi = du_cur;
+        du_cur = du_lo;
         u_hi = u_cur;
         u_cur = u_lo;
       }
-      // defect of this interval: |c|_1 and its weighted propagation to the last node, Psi_s c_s
-      {
-        R c[NX];
-        unpack<R, NX>(a.cs[(int64_t)s * st + p], c);
-#pragma unroll
-        for (int t = 0; t < NX; ++t) cn += Math<R>::fabs(c[t]);
-#pragma unroll
-        for (int r = 0; r < NX; ++r) {
-          W acc = (W)Psi[r][0] * (W)c[0];
-#pragma unroll
-          for (int m = 1; m < NX; ++m) acc += (W)Psi[r][m] * (W)c[m];
-          ha[r] += acc;
-        }
-      }
-      // Psi <- Psi Phi_s
-      R Ph[NX][NX];
-      Q T[NX][NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], Ph[r]);
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) {
-          Q acc = Psi[r][0] * Q(Ph[0][c]);
-#pragma unroll
-          for (int m = 1; m < NX; ++m) acc += Psi[r][m] * Q(Ph[m][c]);
-          T[r][c] = acc;
-        }
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+      phi_transpose_times(a.Phi, s, st, p, lamv);
     }
-    // Psi is now diag(w) Phi_{S-2}...Phi_0: contribution of dx_0 = -c_init
+  }
+  R rq[NX], dq[NX];  // (S + Dg) dq = viol - rho' with the factors of the first solve
+#pragma unroll
+  for (int t = 0; t < NX; ++t) rq[t] = viol[t] - rho2[t];
+  ldl.solve(rq, dq);
+#pragma unroll
+  for (int t = 0; t < NX; ++t) q[t] += dq[t];  // the multipliers of the next pass's adjoint
+  // ascending: the correction of the step, applied; the directional quantities from the corrected step
+  gd = R(0);
+  curv = R(0);
+  dz_inf = R(0);
+  R ddx[NX];
+#pragma unroll
+  for (int t = 0; t < NX; ++t) {
+    ddx[t] = R(0);  // dx_0 = -c_init is exact
+    dz_inf = nan_max(dz_inf, Math<R>::fabs(ci[t]));
+  }
+  R ddu_prev = R(0), du_prev = R(0), ups_prev = R(0);
+  int kk = 0;
+  for (int s = 0; s + 1 < S; ++s) {
+    R acc[NX];
 #pragma unroll
     for (int r = 0; r < NX; ++r) {
-      W acc = (W)Psi[r][0] * (W)ci[0];
+      R row[NX];
+      unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
+      R v = R(0);
 #pragma unroll
-      for (int m = 1; m < NX; ++m) acc += (W)Psi[r][m] * (W)ci[m];
-      hv[r] += ha[r] - acc;
+      for (int m = 0; m < NX; ++m) v += row[m] * ddx[m];
+      acc[r] = v;
     }
-  }
-  f *= R(0.5);
-
-  int status = kTermNone;
-  if (!Math<R>::finite(f) || !Math<R>::finite(cn)) status = kTermNonFinite;
-
-  // ---- (S + Dg) q = h - rho by LDL^T on the lower triangle, in registers ------------------------
-  Q q[NX];
-  W Lm[NX][NX], dv[NX], idv[NX];  // (function scope: the refinement after sweep 2 solves with them again)
-  {
+    for (int i = 0; i < SP; ++i, ++kk) {
+      R G[NX], Wr[NX];
+      unpack<R, NX>(a.Gam[(int64_t)kk * st + p], G);
+      unpack<R, NX>(a.Wk[(int64_t)kk * st + p], Wr);
+      const V4 T = a.Tk[(int64_t)kk * st + p];
+      const R ddu = -(T.x + dot<R>(Wr, dq)) * T.z - ups_prev * ddu_prev;
+      const R du = a.dzu[(int64_t)kk * st + p] + ddu;
+      a.dzu[(int64_t)kk * st + p] = du;
+      dz_inf = nan_max(dz_inf, Math<R>::fabs(du));
 #pragma unroll
-    for (int i = 0; i < NX; ++i) Sm[i][i] += WO::of(Dg[i]);
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      W dj = Sm[j][j];
-#pragma unroll
-      for (int m = 0; m < j; ++m) dj -= Lm[j][m] * Lm[j][m] * dv[m];
-      if (!(dj > W(0))) pd_ok = false;
-      dv[j] = dj;
-      W inv;
-      if constexpr (kWidened) inv = wide_inv<R, W>(dj);
-      else inv = R(1) / dj;
-      idv[j] = inv;
-#pragma unroll
-      for (int i = j + 1; i < NX; ++i) {
-        W v = Sm[i][j];
-#pragma unroll
-        for (int m = 0; m < j; ++m) v -= Lm[i][m] * Lm[j][m] * dv[m];
-        Lm[i][j] = v * inv;
-      }
+      for (int r = 0; r < NX; ++r) acc[r] += G[r] * ddu;
+      gd += T.w * du;
+      const R jd = a.wd * (du_prev - du);
+      curv += wu2 * du * du + jd * jd + lam * du * du;
+      ddu_prev = ddu;
+      du_prev = du;
+      ups_prev = T.y;
     }
-    auto ldl_solve = [&](const W (&b)[NX], W (&x)[NX]) {
-      W y[NX];
-#pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        W v = b[i];
-#pragma unroll
-        for (int m = 0; m < i; ++m) v -= Lm[i][m] * y[m];
-        y[i] = v;
-      }
-#pragma unroll
-      for (int i = NX - 1; i >= 0; --i) {
-        W v;
-        if constexpr (kWidened) v = y[i] * idv[i];
-        else v = y[i] / dv[i];
-#pragma unroll
-        for (int m = i + 1; m < NX; ++m) v -= Lm[m][i] * x[m];
-        x[i] = v;
-      }
-    };
-    W rhs[NX], qw[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) rhs[i] = hv[i] - rho[i];
-    ldl_solve(rhs, qw);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) q[i] = (Q)qw[i];
-    // One step of iterative refinement of q with the residual taken through the factored operator
-    // (S = W^T D^-1 W is a normal-equations matrix; see mpc_fused_body.inc).  fp64 only HERE: this kernel is bound by
-    // its workspace traffic and the pass re-reads W and T from HBM (+25 % bytes); the fused kernel, where the pass is
-    // on-chip, refines in fp32 too, so the two fp32 pipelines differ by that one correction (both are fp32-rounding
-    // level; the parity dtype is fp64, where both refine).
-    if constexpr (sizeof(R) == 8) {
-      R acc[NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) acc[r] = R(0);
-      for (int kk = 0; kk < N; ++kk) {
-        R wk[NX];
-        unpack<R, NX>(a.Wk[(int64_t)kk * st + p], wk);
-        const V4 tk = a.Tk[(int64_t)kk * st + p];
-        R om = wk[0] * q[0];
-#pragma unroll
-        for (int r = 1; r < NX; ++r) om += wk[r] * q[r];
-        const R t = om * tk.z;  // (w_k . q) / d_k
-#pragma unroll
-        for (int r = 0; r < NX; ++r) acc[r] += wk[r] * t;
-      }
-      R rq[NX], dq[NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) rq[r] = rhs[r] - Dg[r] * q[r] - acc[r];
-      ldl_solve(rq, dq);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) q[r] += dq[r];
-    }
-  }
-  if (status == kTermNone && !pd_ok) status = kTermQpIndefinite;
-
-  // ---- sweep 1b (wide QP only; k descending): y_k = -(gw_k + w_k . q) in double, left in the slot of gw_k -------------
-  if constexpr (kWideQP) {
-    Q psi[NX];
-#pragma unroll
-    for (int c = 0; c < NX; ++c) psi[c] = Q(Rw[c]) * q[c];  // Psi_{S-2}^T q, Psi_{S-2} = diag(w)
-    Q om = Q(0);
-    int kk = N - 1;
-    for (int s = S - 2; s >= 0; --s) {
-      for (int i = SP - 1; i >= 0; --i, --kk) {
-        R gk[NX];
-        unpack<R, NX>(a.Gam[(int64_t)kk * st + p], gk);
-        V4 T = a.Tk[(int64_t)kk * st + p];
-        Q pg = psi[0] * Q(gk[0]);
-#pragma unroll
-        for (int m = 1; m < NX; ++m) pg += psi[m] * Q(gk[m]);
-        om = pg - Q(T.y) * om;                 // w_k . q
-        T.x = (R)(-(Q(T.x) + om));             // y_k
-        a.Tk[(int64_t)kk * st + p] = T;
-      }
-      // psi <- Phi_s^T psi for the interval below
-      Q pn[NX];
-#pragma unroll
-      for (int c = 0; c < NX; ++c) pn[c] = Q(0);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
-#pragma unroll
-        for (int c = 0; c < NX; ++c) pn[c] += Q(row[c]) * psi[r];
-      }
-#pragma unroll
-      for (int c = 0; c < NX; ++c) psi[c] = pn[c];
-    }
-  }
-
-  // ---- sweep 2 (k ascending): U^T du = D^-1 y, state recovery, directional quantities -----------
-  R gd = R(0), curv = R(0);
-  R dz_inf = R(0);  // |dz|_inf, for the full-step rule of the line search (nan_max drops a NaN component: see above)
-  {
-    R dx[NX];
+    R xn[NX];
+    unpack<R, NX>(a.dzx[(int64_t)(s + 1) * st + p], xn);
 #pragma unroll
     for (int t = 0; t < NX; ++t) {
-      dx[t] = -ci[t];
-      dz_inf = nan_max(dz_inf, Math<R>::fabs(dx[t]));
+      ddx[t] = acc[t];
+      xn[t] += acc[t];
+      dz_inf = nan_max(dz_inf, Math<R>::fabs(xn[t]));
     }
-    a.dzx[p] = pack<R, NX>(dx);
-    R du_prev = R(0);   // du_{k-1}; the (u_0 - u_prev) row sees only du_0
-    R ups_prev = R(0);  // upsilon_{k-1}
-    const XVn* __restrict__ w_p = a.Wk + p;
-    const V4* __restrict__ t_p = a.Tk + p;
-    const XVn* __restrict__ g_p = a.Gam + p;
-    XVn W_nx, G_nx = g_p[0];  // software pipeline, one column ahead
-    if constexpr (!kWideQP) W_nx = w_p[0];
-    V4 T_nx = t_p[0];
-    int kk = 0;
-    for (int s = 0; s + 1 < S; ++s) {
-      R acc[NX];
-      unpack<R, NX>(a.cs[(int64_t)s * st + p], acc);
+    a.dzx[(int64_t)(s + 1) * st + p] = pack<R, NX>(xn);
 #pragma unroll
-      for (int r = 0; r < NX; ++r) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
-#pragma unroll
-        for (int m = 0; m < NX; ++m) acc[r] += row[m] * dx[m];
-      }
-      for (int i = 0; i < SP; ++i, ++kk) {
-        R G[NX];
-        unpack<R, NX>(G_nx, G);
-        const V4 T = T_nx;
-        R y;
-        if constexpr (kWideQP) {
-          y = T.x;  // sweep 1b left y_k here
-        } else {
-          R Wr[NX];
-          unpack<R, NX>(W_nx, Wr);
-          R wq = Wr[0] * (R)q[0];
-#pragma unroll
-          for (int m = 1; m < NX; ++m) wq += Wr[m] * (R)q[m];
-          y = -(T.x + wq);
-        }
-        if (kk + 1 < N) {
-          if constexpr (!kWideQP) W_nx = w_p[(int64_t)(kk + 1) * st];
-          T_nx = t_p[(int64_t)(kk + 1) * st];
-          G_nx = g_p[(int64_t)(kk + 1) * st];
-        }
-        const R du = y * T.z - ups_prev * du_prev;
-        a.dzu[(int64_t)kk * st + p] = du;
-        dz_inf = nan_max(dz_inf, Math<R>::fabs(du));
-#pragma unroll
-        for (int r = 0; r < NX; ++r) acc[r] += G[r] * du;
-        gd += T.w * du;
-        const R jd = a.wd * (du_prev - du);  // rows (u_{k-1} - u_k) w and, for k = 0, (u_0 - u_prev) w
-        curv += wu2 * du * du + jd * jd + lam * du * du;
-        du_prev = du;
-        ups_prev = T.y;
-      }
-#pragma unroll
-      for (int t = 0; t < NX; ++t) {
-        dx[t] = acc[t];
-        dz_inf = nan_max(dz_inf, Math<R>::fabs(dx[t]));
-      }
-      a.dzx[(int64_t)(s + 1) * st + p] = pack<R, NX>(dx);
-    }
-#pragma unroll
-    for (int t = 0; t < NX; ++t) {
-      if (Dg[t] != R(0)) {
-        const R jd = Rw[t] * dx[t];
-        gd += (Rw[t] * e_term[t]) * jd;
-        curv += jd * jd;
-      }
-    }
-    // ---- one step of iterative refinement of the whole QP solution (CPMPC_CREATE_REFINE_QP; see the block after
-    // sweep 2 in mpc_fused_body.inc for the why): residuals of the terminal rows and of stationarity in the ORIGINAL
-    // data at the recovered (du, dx), the adjoint walked back through Phi^T; a second solve with the same factors;
-    // du, dx and the directional quantities replaced by the corrected ones.  Two more passes over the workspace.
-    if constexpr (sizeof(R) == 8 && !kWidened) {
-      // a.refine_qp passes (1: CPMPC_CREATE_REFINE_QP; 2 beyond cpmpc_max_parity_horizon(), round 6): every pass re-evaluates
-      // the residuals at the corrected (du, dx, q) and solves once more with the same factors -- iterative refinement of the
-      // KKT system with the condensed solve as the approximate inverse: each pass multiplies a lane's error by that solve's
-      // relative error on the lane (1e-3 at worst at 1.6 s), where the condensed solve alone is left with it.
-#pragma unroll 1
-      for (int pass = 0; pass < a.refine_qp; ++pass) {
-        R viol[NX], lamv[NX];
-#pragma unroll
-        for (int t = 0; t < NX; ++t) {
-          const R rT = Rw[t] * (dx[t] + e_term[t]);
-          const bool cost = Dg[t] != R(0);
-          lamv[t] = Rw[t] * (cost ? rT : q[t]);  // the adjoint at the terminal node, diag(Rw) mult
-          viol[t] = cost ? R(0) : rT;
-        }
-        R rho2[NX];
-#pragma unroll
-        for (int t = 0; t < NX; ++t) rho2[t] = R(0);
-        {  // descending: rstat_k = (T du)_k + g_k + Gamma_k . lambda_s, gw'_k = rstat_k - ups_k gw'_{k+1}, rho' += w_k gw'_k / d_k
-          R gw_next = R(0);
-          R du_hi = R(0), du_cur = a.dzu[(int64_t)(N - 1) * st + p];
-          R u_hi = R(0), u_cur = a.zu[(int64_t)(N - 1) * st + p];
-          int k2 = N - 1;
-          for (int s = S - 2; s >= 0; --s) {
-            for (int i = SP - 1; i >= 0; --i, --k2) {
-              const bool inner = k2 < N - 1;
-              const R du_lo = (k2 > 0) ? a.dzu[(int64_t)(k2 - 1) * st + p] : R(0);
-              const R u_lo = (k2 > 0) ? a.zu[(int64_t)(k2 - 1) * st + p] : u_prev;
-              R g = wu2 * u_cur + wd2 * (u_cur - u_lo);
-              if (inner) g += wd2 * (u_cur - u_hi);
-              R G[NX], Wr[NX];
-              unpack<R, NX>(a.Gam[(int64_t)k2 * st + p], G);
-              unpack<R, NX>(a.Wk[(int64_t)k2 * st + p], Wr);
-              V4 T = a.Tk[(int64_t)k2 * st + p];
-              R rstat = (wu2 + lam + wd2 * ((inner ? R(1) : R(0)) + R(1))) * du_cur - wd2 * du_lo + g;
-              if (inner) rstat -= wd2 * du_hi;
-#pragma unroll
-              for (int m = 0; m < NX; ++m) rstat += G[m] * lamv[m];
-              const R gw2 = rstat - T.y * gw_next;
-              const R t2 = gw2 * T.z;
-#pragma unroll
-              for (int m = 0; m < NX; ++m) rho2[m] += Wr[m] * t2;
-              T.x = gw2;
-              a.Tk[(int64_t)k2 * st + p] = T;
-              gw_next = gw2;
-              du_hi = du_cur;
-              du_cur = du_lo;
-              u_hi = u_cur;
-              u_cur = u_lo;
-            }
-            R ln[NX];
-#pragma unroll
-            for (int c = 0; c < NX; ++c) ln[c] = R(0);
-#pragma unroll
-            for (int r = 0; r < NX; ++r) {
-              R row[NX];
-              unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
-#pragma unroll
-              for (int c = 0; c < NX; ++c) ln[c] += row[c] * lamv[r];
-            }
-#pragma unroll
-            for (int c = 0; c < NX; ++c) lamv[c] = ln[c];
-          }
-        }
-        R dq[NX];
-        {  // (S + Dg) dq = viol - rho' with the factors of the first solve
-          R y[NX];
-#pragma unroll
-          for (int i = 0; i < NX; ++i) {
-            R v = viol[i] - rho2[i];
-#pragma unroll
-            for (int m = 0; m < i; ++m) v -= Lm[i][m] * y[m];
-            y[i] = v;
-          }
-#pragma unroll
-          for (int i = NX - 1; i >= 0; --i) {
-            R v = y[i] / dv[i];
-#pragma unroll
-            for (int m = i + 1; m < NX; ++m) v -= Lm[m][i] * dq[m];
-            dq[i] = v;
-          }
-        }
-#pragma unroll
-        for (int t = 0; t < NX; ++t) q[t] += dq[t];  // the multipliers of the next pass's adjoint
-        // ascending: the correction of the step, applied; the directional quantities from the corrected step
-        gd = R(0);
-        curv = R(0);
-        dz_inf = R(0);
-        R ddx[NX];
-#pragma unroll
-        for (int t = 0; t < NX; ++t) {
-          ddx[t] = R(0);  // dx_0 = -c_init is exact
-          dz_inf = nan_max(dz_inf, Math<R>::fabs(ci[t]));
-        }
-        R ddu_prev = R(0), du_prev2 = R(0), ups_prev2 = R(0);
-        int k3 = 0;
-        for (int s = 0; s + 1 < S; ++s) {
-          R acc[NX];
-#pragma unroll
-          for (int r = 0; r < NX; ++r) {
-            R row[NX];
-            unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
-            R v = R(0);
-#pragma unroll
-            for (int m = 0; m < NX; ++m) v += row[m] * ddx[m];
-            acc[r] = v;
-          }
-          for (int i = 0; i < SP; ++i, ++k3) {
-            R G[NX], Wr[NX];
-            unpack<R, NX>(a.Gam[(int64_t)k3 * st + p], G);
-            unpack<R, NX>(a.Wk[(int64_t)k3 * st + p], Wr);
-            const V4 T = a.Tk[(int64_t)k3 * st + p];
-            R wq = Wr[0] * dq[0];
-#pragma unroll
-            for (int m = 1; m < NX; ++m) wq += Wr[m] * dq[m];
-            const R ddu = -(T.x + wq) * T.z - ups_prev2 * ddu_prev;
-            const R du = a.dzu[(int64_t)k3 * st + p] + ddu;
-            a.dzu[(int64_t)k3 * st + p] = du;
-            dz_inf = nan_max(dz_inf, Math<R>::fabs(du));
-#pragma unroll
-            for (int r = 0; r < NX; ++r) acc[r] += G[r] * ddu;
-            gd += T.w * du;
-            const R jd = a.wd * (du_prev2 - du);
-            curv += wu2 * du * du + jd * jd + lam * du * du;
-            ddu_prev = ddu;
-            du_prev2 = du;
-            ups_prev2 = T.y;
-          }
-          R xn[NX];
-          unpack<R, NX>(a.dzx[(int64_t)(s + 1) * st + p], xn);
-#pragma unroll
-          for (int t = 0; t < NX; ++t) {
-            ddx[t] = acc[t];
-            xn[t] += acc[t];
-            dz_inf = nan_max(dz_inf, Math<R>::fabs(xn[t]));
-          }
-          a.dzx[(int64_t)(s + 1) * st + p] = pack<R, NX>(xn);
-#pragma unroll
-          for (int t = 0; t < NX; ++t) dx[t] = xn[t];
-        }
-#pragma unroll
-        for (int t = 0; t < NX; ++t) {
-          if (Dg[t] != R(0)) {
-            const R jd = Rw[t] * dx[t];
-            gd += (Rw[t] * e_term[t]) * jd;
-            curv += jd * jd;
-          }
-        }
-      }
-    }
+    for (int t = 0; t < NX; ++t) dx[t] = xn[t];
   }
-  if (status == kTermNone && (!Math<R>::finite(gd) || !Math<R>::finite(curv))) status = kTermQpIndefinite;
+  terminal_directional<R, NX>(Rw, Dg, e_term, dx, gd, curv);
+}
 
+// The merit at the iterate, the l1-penalty update, the Armijo line search with quadratic-interpolation backtracking from
+// the remembered step length, then accept / reject: the iterate, the step-length memory, the damping schedule, the
+// termination status and the per-problem solver state are written back.
+template <typename R, typename M>
+__device__ __forceinline__ void line_search_and_accept(const SolverArgs<R, M>& a, const typename M::Consts& k,
+                                                       const unsigned p, const R (&xm)[M::NX], const R (&tgt)[M::NX],
+                                                       const R (&e_term)[M::NX], const R u_prev, int status, R f, R cn,
+                                                       const R gd, const R curv, const R dz_inf, R lam, R mu, R a_start) {
+  constexpr int NX = M::NX;
+  const int64_t st = a.stride;
+  const int N = a.N, S = a.S;
   // ---- the merit at the iterate, evaluated the way the trials are --------------------------------------------
-  // f and cn above come out of the linearisation (RK4 with sensitivities, sums in sweep order); the line search
+  // f and cn of the caller come out of the linearisation (RK4 with sensitivities, sums in sweep order); the line search
   // evaluates its trial points with the Jacobian-free rollout in another order of operations.  Both are correct to
   // rounding, but comparing phi(trial) from one path against phi(iterate) from the other puts a path-to-path rounding
   // difference (~1e-13 relative, ~1e-10 absolute at f ~ 1e3) into every Armijo test, and the iteration stalls once
@@ -1255,6 +781,372 @@ __global__ __launch_bounds__(64) void qp_ls_kernel(const SolverArgs<R, M> a) {
   a.ist[IS_STATUS * st + p] = status;
   a.ist[IS_LS_EVALS * st + p] += evals;
   a.ist[IS_FAILED * st + p] = failed;
+}
+
+// ------------------------------------------------------------------------------------------------
+// qp_ls: one thread per problem.  Solves
+//     min 1/2 |J dz + r|^2 + 1/2 lambda |du|^2   s.t.  A dz + c = 0
+// exactly, without forming it: the states are eliminated through the shooting recursion
+//     dx_0 = -c_init,  dx_{s+1} = Phi_s dx_s + Gamma_s du_s + c_s,
+// which leaves a QP in du whose Hessian is T + R^T R with T tridiagonal (control costs) and R the
+// <= NX terminal rows (cost or equality).  The phases of the kernel (the pivot step, the LDL^T and the adjoint
+// products are the blocks of condensed_qp.hpp):
+//   1. residuals at z: the initial-state rows and the terminal rows.
+//   2. sweep 1 (k descending): T = U D U^T by a scalar recurrence; W = U^-1 R^T row by row from
+//           m_k = Psi Gamma_k, Psi = diag(w) Phi_{S-2} ... Phi_{s+1}; gw = U^-1 g; accumulate
+//           S = W^T D^-1 W (NX x NX), rho = W^T D^-1 gw and the weighted free response sum_s Psi_s c_s;
+//           rows of W and {gw, upsilon, 1/d, g} are stored.
+//   3. NX x NX LDL^T of S + diag(1 for cost rows, 0 for equality rows) in registers -> multipliers q (double kernels:
+//           refined once through the factored operator).
+//   4. sweep 1b (wide QP only, k descending): y = -(gw + W q) in double.
+//   5. sweep 2 (k ascending): y = -(gw + W q), U^T du = D^-1 y, state recovery through Phi/Gamma, and the
+//           directional quantities g.du and |J dz|^2.
+//   6. refine_qp_pass (double kernels, a.refine_qp times): refinement of the whole QP solution.
+//   7. line_search_and_accept: the l1-merit penalty update, the Armijo line search, accept / reject.
+// ------------------------------------------------------------------------------------------------
+// The terminal system (S, rho, the weighted free response, the LDL^T and its solve) is carried in the wide type W of
+// wide.hpp: double in a float kernel, R itself in a double kernel.
+// WIDEQ (float handles with CPMPC_CREATE_WIDE_QP, the default for the 6-state model; round 6): as in the fused kernel (type Q
+// of mpc_fused_body.inc), everything between the linearisation and the multipliers' effect on the step is carried in double
+// too -- the Psi products across the intervals, the columns w_k of U^-1 R^T, psi = Psi^T q and y = -(gw + W q).  W is then
+// never read back in float: after the multipliers are known a pass of its own ("sweep 1b", k descending) forms
+//     w_k . q = psi_s . Gamma_k - ups_k (w_{k+1} . q),   psi_s = Phi_{s+1}^T psi_{s+1},  psi_{S-2} = diag(w) q
+// in double and leaves y_k in the slot of (U^-1 g)_k.  One more pass over Gamma, Phi and T than the plain kernel: this
+// pipeline is the fall-back for shapes the fused kernel is not built for, correctness is its bar, not throughput.
+template <typename R, typename M, bool WIDEQ = false>
+__global__ __launch_bounds__(64) void qp_ls_kernel(const SolverArgs<R, M> a) {
+  using V4 = typename VecT<R>::V4;
+  using XVn = XV<R, M::NX>;
+  using W = typename WideOf<R>::type;
+  using WO = Wide<W>;
+  constexpr bool kWidened = !std::is_same<W, R>::value;
+  constexpr bool kWideQP = WIDEQ && kWidened;
+  using Q = std::conditional_t<kWideQP, W, R>;
+  constexpr int NX = M::NX;
+  const unsigned p = blockIdx.x * 64u + threadIdx.x;
+  if (p >= a.B) return;
+  const int64_t st = a.stride;
+  if (a.ist[IS_STATUS * st + p] != kTermNone) return;
+  const typename M::Consts k = load_consts(a, p);
+  const int N = a.N, S = a.S, SP = a.SP;
+
+  const R lam = a.sc[SC_LAMBDA * st + p];
+  const R mu = a.sc[SC_MU * st + p];
+  const R u_prev = a.sc[SC_UPREV * st + p];
+  const R a_start = a.sc[SC_ALPHA * st + p];
+  R tgt[NX], xm[NX];
+#pragma unroll
+  for (int t = 0; t < NX; ++t) {
+    tgt[t] = a.term_tgt[t];
+    xm[t] = a.x0[t * a.B + p];
+  }
+  if (a.set_point) tgt[0] = a.set_point[p];
+
+  const R wu2 = a.wu * a.wu, wd2 = a.wd * a.wd;
+
+  // ---- 1. residuals at z: initial-state rows, terminal rows --------------------------------------
+  R f = R(0), cn = R(0);
+  R ci[NX];
+  {
+    R z0[NX];
+    unpack<R, NX>(a.zx[p], z0);
+#pragma unroll
+    for (int t = 0; t < NX; ++t) ci[t] = z0[t] - xm[t];
+    wrap_angles<R, M>(ci);
+#pragma unroll
+    for (int t = 0; t < NX; ++t) cn += Math<R>::fabs(ci[t]);
+  }
+  // The weighted free response  ha = diag(w) dx_{S-1}|_{du=0} = sum_s Psi_s c_s - Psi_{-1} c_init  is
+  // accumulated inside sweep 1, where Psi_s = diag(w) Phi_{S-2}...Phi_{s+1} is available anyway.
+  W hv[NX];
+  R Rw[NX], Dg[NX], e_term[NX];
+  {
+    R zt[NX];
+    unpack<R, NX>(a.zx[(int64_t)(S - 1) * st + p], zt);
+#pragma unroll
+    for (int t = 0; t < NX; ++t) e_term[t] = zt[t] - tgt[t];
+    wrap_angles<R, M>(e_term);
+    load_terminal<R, M>(a, p, Rw, Dg);
+#pragma unroll
+    for (int t = 0; t < NX; ++t) {
+      const bool is_cost = Dg[t] != R(0);
+      if (is_cost) {
+        const R r = Rw[t] * e_term[t];
+        f += r * r;
+      } else {
+        cn += Math<R>::fabs(e_term[t]);
+      }
+      hv[t] = WO::prod(Rw[t], e_term[t]);  // + ha[t], added after sweep 1
+    }
+  }
+
+  // ---- 2. sweep 1 (k descending) ----------------------------------------------------------------
+  W Sm[NX][NX], rho[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) {
+    rho[i] = WO::of(R(0));
+#pragma unroll
+    for (int j = 0; j < NX; ++j) Sm[i][j] = WO::of(R(0));
+  }
+  bool pd_ok = true;
+  {
+    Q Psi[NX][NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
+    Q wprev[NX];
+    W ha[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) {
+      wprev[r] = Q(0);
+      ha[r] = WO::of(R(0));
+    }
+    R gwprev = R(0);
+    R d_next = R(1);
+    const XVn* __restrict__ gam_p = a.Gam + p;
+    const R* __restrict__ zu_p = a.zu + p;
+    R u_hi = R(0);                              // u_{k+1}
+    R u_cur = zu_p[(int64_t)(N - 1) * st];      // u_k
+    // software pipeline: the loads of column k-1 are issued before column k is consumed
+    XVn G_nx = gam_p[(int64_t)(N - 1) * st];
+    R u_nx = (N > 1) ? zu_p[(int64_t)(N - 2) * st] : u_prev;
+    int kk = N - 1;
+    for (int s = S - 2; s >= 0; --s) {
+      for (int i = SP - 1; i >= 0; --i, --kk) {
+        R gk[NX];
+        unpack<R, NX>(G_nx, gk);
+        const R u_lo = u_nx;  // u_{k-1} (u_prev for k = 0)
+        if (kk > 0) {
+          G_nx = gam_p[(int64_t)(kk - 1) * st];
+          u_nx = (kk > 1) ? zu_p[(int64_t)(kk - 2) * st] : u_prev;
+        }
+        // control cost rows at z, tridiagonal entries and the control-cost gradient g_k
+        const R ru = a.wu * u_cur, rd = a.wd * (u_lo - u_cur);
+        f += ru * ru + rd * rd;
+        R g = wu2 * u_cur + wd2 * (u_cur - u_lo);
+        if (kk < N - 1) g += wd2 * (u_cur - u_hi);
+        // U D U^T recurrence (off-diagonal of T is -wd2)
+        R ups, dk, inv_d;
+        tridiag_pivot(kk, N, wu2, wd2, lam, d_next, ups, dk, inv_d);
+        if (!(dk > R(0))) pd_ok = false;
+        d_next = dk;
+        // m_k = Psi Gamma_k ; w_k = m_k - ups w_{k+1}
+        Q wk[NX];
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+          Q m = Psi[r][0] * Q(gk[0]);
+#pragma unroll
+          for (int c = 1; c < NX; ++c) m += Psi[r][c] * Q(gk[c]);
+          wk[r] = m - Q(ups) * wprev[r];
+        }
+        const R gw = g - ups * gwprev;
+        if constexpr (!kWideQP) {  // (the wide kernel never reads W back: sweep 1b below)
+          R wk_r[NX];
+#pragma unroll
+          for (int r = 0; r < NX; ++r) wk_r[r] = (R)wk[r];
+          a.Wk[(int64_t)kk * st + p] = pack<R, NX>(wk_r);
+        }
+        a.Tk[(int64_t)kk * st + p] = mk4<R>(gw, ups, inv_d, g);
+#pragma unroll
+        for (int i2 = 0; i2 < NX; ++i2) {
+          const W wi = (W)wk[i2] * (W)inv_d;  // exact in W for float columns: S is the Gram matrix of the rounded rows (wide.hpp)
+          rho[i2] += wi * gw;
+#pragma unroll
+          for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
+        }
+#pragma unroll
+        for (int r = 0; r < NX; ++r) wprev[r] = wk[r];
+        gwprev = gw;
+        u_hi = u_cur;
+        u_cur = u_lo;
+      }
+      // defect of this interval: |c|_1 and its weighted propagation to the last node, Psi_s c_s
+      {
+        R c[NX];
+        unpack<R, NX>(a.cs[(int64_t)s * st + p], c);
+#pragma unroll
+        for (int t = 0; t < NX; ++t) cn += Math<R>::fabs(c[t]);
+#pragma unroll
+        for (int r = 0; r < NX; ++r) {
+          W acc = (W)Psi[r][0] * (W)c[0];
+#pragma unroll
+          for (int m = 1; m < NX; ++m) acc += (W)Psi[r][m] * (W)c[m];
+          ha[r] += acc;
+        }
+      }
+      // Psi <- Psi Phi_s
+      R Ph[NX][NX];
+      Q T[NX][NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], Ph[r]);
+#pragma unroll
+      for (int r = 0; r < NX; ++r)
+#pragma unroll
+        for (int c = 0; c < NX; ++c) {
+          Q acc = Psi[r][0] * Q(Ph[0][c]);
+#pragma unroll
+          for (int m = 1; m < NX; ++m) acc += Psi[r][m] * Q(Ph[m][c]);
+          T[r][c] = acc;
+        }
+#pragma unroll
+      for (int r = 0; r < NX; ++r)
+#pragma unroll
+        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+    }
+    // Psi is now diag(w) Phi_{S-2}...Phi_0: contribution of dx_0 = -c_init
+#pragma unroll
+    for (int r = 0; r < NX; ++r) {
+      W acc = (W)Psi[r][0] * (W)ci[0];
+#pragma unroll
+      for (int m = 1; m < NX; ++m) acc += (W)Psi[r][m] * (W)ci[m];
+      hv[r] += ha[r] - acc;
+    }
+  }
+  f *= R(0.5);
+
+  int status = kTermNone;
+  if (!Math<R>::finite(f) || !Math<R>::finite(cn)) status = kTermNonFinite;
+
+  // ---- 3. (S + Dg) q = h - rho by LDL^T on the lower triangle, in registers ----------------------
+  Q q[NX];
+  TerminalLDL<R, NX> ldl;  // (function scope: the refinement after sweep 2 solves with the factors again)
+  {
+#pragma unroll
+    for (int i = 0; i < NX; ++i) Sm[i][i] += WO::of(Dg[i]);
+    if (!ldl.factor(Sm)) pd_ok = false;
+    W rhs[NX], qw[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) rhs[i] = hv[i] - rho[i];
+    ldl.solve(rhs, qw);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) q[i] = (Q)qw[i];
+    // One step of iterative refinement of q with the residual taken through the factored operator
+    // (S = W^T D^-1 W is a normal-equations matrix; see mpc_fused_body.inc).  fp64 only HERE: this kernel is bound by
+    // its workspace traffic and the pass re-reads W and T from HBM (+25 % bytes); the fused kernel, where the pass is
+    // on-chip, refines in fp32 too, so the two fp32 pipelines differ by that one correction (both are fp32-rounding
+    // level; the parity dtype is fp64, where both refine).
+    if constexpr (sizeof(R) == 8) {
+      R acc[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) acc[r] = R(0);
+      for (int kk = 0; kk < N; ++kk) {
+        R wk[NX];
+        unpack<R, NX>(a.Wk[(int64_t)kk * st + p], wk);
+        const V4 tk = a.Tk[(int64_t)kk * st + p];
+        const R t = dot<R>(wk, q) * tk.z;  // (w_k . q) / d_k
+#pragma unroll
+        for (int r = 0; r < NX; ++r) acc[r] += wk[r] * t;
+      }
+      R rq[NX], dq[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) rq[r] = rhs[r] - Dg[r] * q[r] - acc[r];
+      ldl.solve(rq, dq);
+#pragma unroll
+      for (int r = 0; r < NX; ++r) q[r] += dq[r];
+    }
+  }
+  if (status == kTermNone && !pd_ok) status = kTermQpIndefinite;
+
+  // ---- 4. sweep 1b (wide QP only; k descending): y_k = -(gw_k + w_k . q) in double, left in the slot of gw_k ----------
+  if constexpr (kWideQP) {
+    Q psi[NX];
+#pragma unroll
+    for (int c = 0; c < NX; ++c) psi[c] = Q(Rw[c]) * q[c];  // Psi_{S-2}^T q, Psi_{S-2} = diag(w)
+    Q om = Q(0);
+    int kk = N - 1;
+    for (int s = S - 2; s >= 0; --s) {
+      for (int i = SP - 1; i >= 0; --i, --kk) {
+        R gk[NX];
+        unpack<R, NX>(a.Gam[(int64_t)kk * st + p], gk);
+        V4 T = a.Tk[(int64_t)kk * st + p];
+        const Q pg = dot<Q>(psi, gk);
+        om = pg - Q(T.y) * om;                 // w_k . q
+        T.x = (R)(-(Q(T.x) + om));             // y_k
+        a.Tk[(int64_t)kk * st + p] = T;
+      }
+      phi_transpose_times(a.Phi, s, st, p, psi);  // for the interval below
+    }
+  }
+
+  // ---- 5. sweep 2 (k ascending): U^T du = D^-1 y, state recovery, directional quantities ---------
+  R gd = R(0), curv = R(0);
+  R dz_inf = R(0);  // |dz|_inf, for the full-step rule of the line search (nan_max drops a NaN component: see above)
+  {
+    R dx[NX];
+#pragma unroll
+    for (int t = 0; t < NX; ++t) {
+      dx[t] = -ci[t];
+      dz_inf = nan_max(dz_inf, Math<R>::fabs(dx[t]));
+    }
+    a.dzx[p] = pack<R, NX>(dx);
+    R du_prev = R(0);   // du_{k-1}; the (u_0 - u_prev) row sees only du_0
+    R ups_prev = R(0);  // upsilon_{k-1}
+    const XVn* __restrict__ w_p = a.Wk + p;
+    const V4* __restrict__ t_p = a.Tk + p;
+    const XVn* __restrict__ g_p = a.Gam + p;
+    XVn W_nx, G_nx = g_p[0];  // software pipeline, one column ahead
+    if constexpr (!kWideQP) W_nx = w_p[0];
+    V4 T_nx = t_p[0];
+    int kk = 0;
+    for (int s = 0; s + 1 < S; ++s) {
+      R acc[NX];
+      unpack<R, NX>(a.cs[(int64_t)s * st + p], acc);
+#pragma unroll
+      for (int r = 0; r < NX; ++r) {
+        R row[NX];
+        unpack<R, NX>(a.Phi[(int64_t)(NX * s + r) * st + p], row);
+#pragma unroll
+        for (int m = 0; m < NX; ++m) acc[r] += row[m] * dx[m];
+      }
+      for (int i = 0; i < SP; ++i, ++kk) {
+        R G[NX];
+        unpack<R, NX>(G_nx, G);
+        const V4 T = T_nx;
+        R y;
+        if constexpr (kWideQP) {
+          y = T.x;  // sweep 1b left y_k here
+        } else {
+          R Wr[NX];
+          unpack<R, NX>(W_nx, Wr);
+          y = -(T.x + dot<R>(Wr, q));
+        }
+        if (kk + 1 < N) {
+          if constexpr (!kWideQP) W_nx = w_p[(int64_t)(kk + 1) * st];
+          T_nx = t_p[(int64_t)(kk + 1) * st];
+          G_nx = g_p[(int64_t)(kk + 1) * st];
+        }
+        const R du = y * T.z - ups_prev * du_prev;
+        a.dzu[(int64_t)kk * st + p] = du;
+        dz_inf = nan_max(dz_inf, Math<R>::fabs(du));
+#pragma unroll
+        for (int r = 0; r < NX; ++r) acc[r] += G[r] * du;
+        gd += T.w * du;
+        const R jd = a.wd * (du_prev - du);  // rows (u_{k-1} - u_k) w and, for k = 0, (u_0 - u_prev) w
+        curv += wu2 * du * du + jd * jd + lam * du * du;
+        du_prev = du;
+        ups_prev = T.y;
+      }
+#pragma unroll
+      for (int t = 0; t < NX; ++t) {
+        dx[t] = acc[t];
+        dz_inf = nan_max(dz_inf, Math<R>::fabs(dx[t]));
+      }
+      a.dzx[(int64_t)(s + 1) * st + p] = pack<R, NX>(dx);
+    }
+    terminal_directional<R, NX>(Rw, Dg, e_term, dx, gd, curv);
+    // ---- 6. refinement of the whole QP solution: a.refine_qp passes (1: CPMPC_CREATE_REFINE_QP; 2 beyond
+    // cpmpc_max_parity_horizon(), round 6), each re-evaluating the residuals at the corrected (du, dx, q)
+    if constexpr (sizeof(R) == 8 && !kWidened) {
+#pragma unroll 1
+      for (int pass = 0; pass < a.refine_qp; ++pass)
+        refine_qp_pass<R, M>(a, p, wu2, wd2, lam, u_prev, Rw, Dg, e_term, ci, ldl, q, dx, gd, curv, dz_inf);
+    }
+  }
+  if (status == kTermNone && (!Math<R>::finite(gd) || !Math<R>::finite(curv))) status = kTermQpIndefinite;
+
+  // ---- 7. penalty update, line search, accept / reject -------------------------------------------
+  line_search_and_accept<R, M>(a, k, p, xm, tgt, e_term, u_prev, status, f, cn, gd, curv, dz_inf, lam, mu, a_start);
 }
 
 // ------------------------------------------------------------------------------------------------
