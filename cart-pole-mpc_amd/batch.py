@@ -302,6 +302,56 @@ class BatchOptimization:
                                                              _stream_ptr()))
         return (K, ok) if want_ok else K
 
+    def plan_sensitivity(self, dyn, n_rows=1, z=None, terminal_weights=None, want=("K", "k_sp", "k_up"), want_ok=False):
+        """How the plan moves with the three inputs that change between two re-plans, rows 0 .. n_rows-1 (include/cpmpc.h:
+        cpmpc_plan_sensitivity_batch): a dict with the entries named in `want` --
+            "K"    [n_rows, nx, B]  du / dx0 (what feedback_gain returns, bitwise),
+            "k_sp" [n_rows, B]      du / dset_point,
+            "k_up" [n_rows, B]      du / du_prev (the control applied before the plan starts),
+        and "ok" [B] int32 with want_ok (0: the problem's QP is not positive definite, its outputs are NaN).  Sensitivities
+        of the unclamped, undamped QP at z, not of the converged solution; arguments as feedback_gain's.  Only what is
+        named is computed; plan_update() applies them to the whole plan."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("K", "k_sp", "k_up") for w in want):
+            raise ValueError("want must name at least one of 'K', 'k_sp', 'k_up'")
+        dev = torch.device("cuda", self.device)
+        if z is not None:
+            _require_cuda_tensor(z, "z", self.dtype)
+            if z.dim() != 2 or z.shape[0] != self.dim:
+                raise ValueError("z must be [dim=%d, B]" % self.dim)
+            B = int(z.shape[1])
+        else:
+            B = self.previous_solution_batch()
+            if B < 1:
+                raise ValueError("plan_sensitivity(z=None) needs a previous solution: step() first, or pass z")
+        n_rows = int(n_rows)
+        inp = capi.GainInputs(struct_size=C.sizeof(capi.GainInputs))
+        if isinstance(dyn, torch.Tensor):
+            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
+            inp.dyn = dyn.data_ptr()
+        else:
+            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
+            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
+        if terminal_weights is not None:
+            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
+            inp.terminal_weights = terminal_weights.data_ptr()
+        inp.z = z.data_ptr() if z is not None else None
+        rows = max(n_rows, 0)
+        res = {}
+        if "K" in want:
+            res["K"] = torch.empty((rows, self.nx, B), dtype=self.dtype, device=dev)
+        for name in ("k_sp", "k_up"):
+            if name in want:
+                res[name] = torch.empty((rows, B), dtype=self.dtype, device=dev)
+        ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
+        with torch.cuda.device(self.device):
+            capi.check(capi.load().cpmpc_plan_sensitivity_batch(self._h, B, C.byref(inp), n_rows, _ptr(res.get("K")),
+                                                                _ptr(res.get("k_sp")), _ptr(res.get("k_up")), _ptr(ok),
+                                                                _stream_ptr()))
+        if want_ok:
+            res["ok"] = ok
+        return res
+
     # -- pipeline selection --------------------------------------------------------------------
     def set_pipeline(self, mode):
         """'auto' | 'split' | 'fused' (include/cpmpc.h: CPMPC_PIPELINE_*)."""
@@ -424,6 +474,45 @@ def feedback_apply(u_nom, K0, x_nom, x, u_limit=300.0, model="single", out=None)
     return out
 
 
+def plan_update(u_nom, K=None, x_nom=None, x=None, k_sp=None, sp_nom=None, sp=None, k_up=None, u_prev_nom=None, u_prev=None,
+                u_limit=300.0, model="single", out=None):
+    """The first-order re-plan of the whole horizon from BatchOptimization.plan_sensitivity()'s outputs, rows k < n_rows:
+    u [n_rows, B] = clamp(u_nom + K . wrap(x - x_nom) + k_sp (sp - sp_nom) + k_up (u_prev - u_prev_nom), +-u_limit).
+    u_nom [n_rows, B]; K [n_rows, nx, B] with x_nom, x [nx, B]; k_sp [n_rows, B] with sp_nom, sp [B]; k_up [n_rows, B] with
+    u_prev_nom, u_prev [B].  A term whose sensitivity is None is absent; out may be u_nom.  One elementwise launch
+    (cpmpc_plan_update_batch)."""
+    m, nx, _ = _model_dims(model)
+    dt = u_nom.dtype
+    _require_cuda_tensor(u_nom, "u_nom", dt)
+    if u_nom.dim() != 2:
+        raise ValueError("u_nom must be [n_rows, B]")
+    n_rows, B = int(u_nom.shape[0]), int(u_nom.shape[1])
+    a = capi.PlanUpdate(struct_size=C.sizeof(capi.PlanUpdate), u_limit=float(u_limit))
+    a.u_nom = u_nom.data_ptr()
+
+    def give(name, t, shape):
+        if t is not None:
+            _require_cuda_tensor(t, name, dt, shape)
+            setattr(a, name, t.data_ptr())
+    give("K", K, (n_rows, nx, B))
+    give("x_nom", x_nom, (nx, B))
+    give("x", x, (nx, B))
+    give("k_sp", k_sp, (n_rows, B))
+    give("sp_nom", sp_nom, (B,))
+    give("sp", sp, (B,))
+    give("k_up", k_up, (n_rows, B))
+    give("u_prev_nom", u_prev_nom, (B,))
+    give("u_prev", u_prev, (B,))
+    if out is None:
+        out = torch.empty((n_rows, B), dtype=dt, device=u_nom.device)
+    else:
+        _require_cuda_tensor(out, "out", dt, (n_rows, B))
+    a.u_out = out.data_ptr()
+    with torch.cuda.device(u_nom.device):
+        capi.check(capi.load().cpmpc_plan_update_batch(_CAPI_DTYPE[dt], m, B, n_rows, C.byref(a), _stream_ptr()))
+    return out
+
+
 class BatchSimulator:
     """B independent pendulum::Simulator plants (optimization/simulator.hpp:10-29)."""
 
@@ -530,18 +619,22 @@ class ClosedLoop:
         st = self.streams[i]
         return torch.cuda.stream(st) if st is not None else torch.cuda.stream(torch.cuda.current_stream(self.device))
 
-    def tick(self, dyn, set_point=0.0, dt=0.01, want_stats=True, substeps=1, fext=None):
+    def tick(self, dyn, set_point=0.0, dt=0.01, want_stats=True, substeps=1, fext=None, set_point_inner=None):
         """One MPC tick of every controller (queued, not waited for).  With feedback=True the plant advances in `substeps`
         steps of dt / substeps, each under u_0 + K[0] . wrap(x - x0) of its current state; fext: optional callable
-        (range index, sub-step) -> [4, n] tensor of external forces on that range's plants for that sub-step."""
-        if not self.feedback and (int(substeps) != 1 or fext is not None):
-            raise ValueError("ClosedLoop.tick: substeps / fext belong to the feedback loop (ClosedLoop(..., feedback=True))")
+        (range index, sub-step) -> [4, n] tensor of external forces on that range's plants for that sub-step.
+        set_point_inner (feedback=True; a float or a [B] tensor): the set-point as it stands during the sub-steps, where it
+        has moved since the plan was made for `set_point`; the sub-steps then apply
+        u_0 + K[0] . wrap(x - x0) + k_sp[0] (set_point_inner - set_point) (BatchOptimization.plan_sensitivity)."""
+        if not self.feedback and (int(substeps) != 1 or fext is not None or set_point_inner is not None):
+            raise ValueError("ClosedLoop.tick: substeps / fext / set_point_inner belong to the feedback loop "
+                             "(ClosedLoop(..., feedback=True))")
         if int(substeps) < 1:
             raise ValueError("substeps must be >= 1")
         if isinstance(dyn, torch.Tensor):
             raise TypeError("ClosedLoop.tick: dyn is the plant's parameter set too (cpmpc_sim_step_batch takes shared host "
                             "parameters): pass the %d numbers, not a tensor" % self.sims[0].np)
-        tensors = [t for t in (set_point,) if isinstance(t, torch.Tensor)]
+        tensors = [t for t in (set_point, set_point_inner) if isinstance(t, torch.Tensor)]
         if len(self.sims) > 1 and (self._inputs_dirty or tensors):
             # whatever prepared the states -- or this tick's per-problem parameters / set-points -- on the caller's stream
             # comes first.  Shared (host) parameters and no set_state since the last tick: no wait, the ranges run free.
@@ -558,21 +651,46 @@ class ClosedLoop:
                 # per-problem set-points [B]: this range's columns (copied on the range's stream)
                 sp = set_point if one or not isinstance(set_point, torch.Tensor) else set_point[lo:hi].contiguous()
                 if self.feedback:
-                    self._tick_feedback(i, s, o, out, dyn, sp, dt, want_stats, int(substeps), fext)
+                    spi = set_point_inner
+                    if isinstance(spi, torch.Tensor) and not one:
+                        spi = spi[lo:hi].contiguous()
+                    self._tick_feedback(i, s, o, out, dyn, sp, dt, want_stats, int(substeps), fext, spi)
                     continue
                 r = o.step(s.get_state(), dyn, sp, want_predicted=False, want_stats=want_stats, out=out)
                 s.step(dyn, dt, r.u[0].contiguous())
         self.ticks += 1
 
-    def _tick_feedback(self, i, s, o, out, dyn, sp, dt, want_stats, substeps, fext):
+    def _tick_feedback(self, i, s, o, out, dyn, sp, dt, want_stats, substeps, fext, sp_inner=None):
         x0 = s.get_state().clone()  # the state the plan is made for: the plant's own tensor moves under the sub-steps
         r = o.step(x0, dyn, sp, want_predicted=False, want_stats=want_stats, out=out)
+        if sp_inner is not None:
+            self._substeps_with_set_point(i, s, o, r, x0, dyn, sp, sp_inner, dt, substeps, fext)
+            return
         K, ok = o.feedback_gain(dyn, n_rows=1, want_ok=True)
         # a controller whose QP is not positive definite has no gain (NaN rows): it holds the plan's u_0, as the plain loop does
         K0 = torch.where(ok.bool().unsqueeze(0), K[0], torch.zeros_like(K[0]))
         u_nom = r.u[0].contiguous()
         for m in range(substeps):
             u = feedback_apply(u_nom, K0, x0, s.get_state(), u_limit=self.u_limit, model=self.model)
+            s.step(dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
+        self.applied[i] = u  # the control of the last sub-step
+
+    def _substeps_with_set_point(self, i, s, o, r, x0, dyn, sp, sp_inner, dt, substeps, fext):
+        """The sub-steps of a tick whose set-point has moved since the plan: K[0] and k_sp[0] from one call, applied by
+        plan_update on row 0.  A lane with ok = 0 holds the plan's u_0."""
+        n = int(x0.shape[1])
+
+        def per_problem(v):
+            return v if isinstance(v, torch.Tensor) else torch.full((n,), float(v), dtype=self.dtype, device=x0.device)
+        sens = o.plan_sensitivity(dyn, n_rows=1, want=("K", "k_sp"), want_ok=True)
+        live = sens["ok"].bool()
+        K = torch.where(live.reshape(1, 1, n), sens["K"], torch.zeros_like(sens["K"]))
+        k_sp = torch.where(live.reshape(1, n), sens["k_sp"], torch.zeros_like(sens["k_sp"]))
+        u_nom = r.u[:1].contiguous()
+        sp_nom, sp_now = per_problem(sp), per_problem(sp_inner)
+        for m in range(substeps):
+            u = plan_update(u_nom, K=K, x_nom=x0, x=s.get_state(), k_sp=k_sp, sp_nom=sp_nom, sp=sp_now,
+                            u_limit=self.u_limit, model=self.model)[0]
             s.step(dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
         self.applied[i] = u  # the control of the last sub-step
 

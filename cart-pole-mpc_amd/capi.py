@@ -45,6 +45,7 @@ SYMBOLS = [
     "cpmpc_sharded_get_solution_host", "cpmpc_sharded_step_batch_host_in", "cpmpc_sharded_step_batch_ex",
     "cpmpc_step_batch_host_in", "cpmpc_set_host_chunk", "cpmpc_host_register", "cpmpc_host_unregister",
     "cpmpc_feedback_gain_batch", "cpmpc_feedback_gain_batch_host", "cpmpc_feedback_apply_batch",
+    "cpmpc_plan_sensitivity_batch", "cpmpc_plan_sensitivity_batch_host", "cpmpc_plan_update_batch",
 ]
 
 
@@ -177,6 +178,26 @@ class GainInputs(C.Structure):
     ]
 
 
+class PlanUpdate(C.Structure):
+    """cpmpc_plan_update: device pointers of cpmpc_plan_update_batch; a sensitivity (K, k_sp, k_up) is given with its pair
+    of nominal / actual arrays or left NULL."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("u_nom", C.c_void_p),
+        ("K", C.c_void_p),
+        ("x_nom", C.c_void_p),
+        ("x", C.c_void_p),
+        ("k_sp", C.c_void_p),
+        ("sp_nom", C.c_void_p),
+        ("sp", C.c_void_p),
+        ("k_up", C.c_void_p),
+        ("u_prev_nom", C.c_void_p),
+        ("u_prev", C.c_void_p),
+        ("u_limit", C.c_double),
+        ("u_out", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -295,6 +316,9 @@ def load():
     L.cpmpc_feedback_gain_batch.argtypes = [vp, i64, C.POINTER(GainInputs), i32, vp, vp, vp]
     L.cpmpc_feedback_gain_batch_host.argtypes = [vp, i64, C.POINTER(GainInputs), i32, _dp, _ip]
     L.cpmpc_feedback_apply_batch.argtypes = [i32, i32, i64, vp, vp, vp, vp, dbl, vp, vp]
+    L.cpmpc_plan_sensitivity_batch.argtypes = [vp, i64, C.POINTER(GainInputs), i32, vp, vp, vp, vp, vp]
+    L.cpmpc_plan_sensitivity_batch_host.argtypes = [vp, i64, C.POINTER(GainInputs), i32, _dp, _dp, _dp, _ip]
+    L.cpmpc_plan_update_batch.argtypes = [i32, i32, i64, i32, C.POINTER(PlanUpdate), vp]
     _lib = L
     return L
 

@@ -851,6 +851,40 @@ extern "C" int cpmpc_feedback_apply_batch(int dtype, int model, int64_t B, const
   return CPMPC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// plan sensitivities, plan update
+// ------------------------------------------------------------------------------------------------
+extern "C" int cpmpc_plan_sensitivity_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K,
+                                            void* k_sp, void* k_up, int32_t* ok, void* stream) {
+  // the gain call's checks, on whichever output was asked for (none: a null argument)
+  int rc = check_gain_args(s, B, in, n_rows, K ? K : (k_sp ? k_sp : k_up));
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  engine_of(s)->plan_sensitivity(s, B, in, n_rows, K, k_sp, k_up, ok, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  track_caller_stream(s, (hipStream_t)stream);  // the workspace (warm start read, scratch written) was used on the caller's stream
+  return CPMPC_OK;
+}
+
+extern "C" int cpmpc_plan_update_batch(int dtype, int model, int64_t B, int n_rows, const cpmpc_plan_update* a,
+                                       void* stream) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  if (a->struct_size != sizeof(cpmpc_plan_update))
+    return fail(CPMPC_ERR_INVALID_ARG, "cpmpc_plan_update.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_plan_update))",
+                (unsigned long long)a->struct_size, sizeof(cpmpc_plan_update));
+  if (!a->u_nom || !a->u_out) return fail(CPMPC_ERR_INVALID_ARG, "null argument (u_nom, u_out)");
+  if (a->K && (!a->x_nom || !a->x)) return fail(CPMPC_ERR_INVALID_ARG, "K is given without x_nom and x");
+  if (a->k_sp && (!a->sp_nom || !a->sp)) return fail(CPMPC_ERR_INVALID_ARG, "k_sp is given without sp_nom and sp");
+  if (a->k_up && (!a->u_prev_nom || !a->u_prev)) return fail(CPMPC_ERR_INVALID_ARG, "k_up is given without u_prev_nom and u_prev");
+  if (!(a->u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no clamp)");
+  if (n_rows < 1 || n_rows > 65535) return fail(CPMPC_ERR_INVALID_ARG, "n_rows must be in [1, 65535]");
+  int rc = check_piece_args(model, dtype, B);
+  if (rc) return rc;
+  engine_for(dtype, model)->plan_update(B, n_rows, a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
+}
+
 // debug builds only (-DCPMPC_FUSED_TIMING / -DCPMPC_FUSED_CLOCK): the counters of fused_sqp_kernel, summed over the
 // kernel translation units (each has its own copies), read and cleared
 static int debug_read_all(int which, unsigned long long* out, int n) {

@@ -335,18 +335,20 @@ extern "C" int cpmpc_get_solution_host(cpmpc_solver* s, int64_t B, double* z_hos
   return get_sol_host_cols(s, B, z_host, B, 0);
 }
 
-// Feedback gains with HOST doubles: one staging slot, [dyn? | terminal_weights? | z? | K | ok] in the handle's dtype, one copy
-// in, the kernels, one copy out, one synchronisation.
-extern "C" int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
-                                              double* K_host, int32_t* ok_host) {
-  int rc = check_gain_args(s, B, in, n_rows, K_host);
-  if (rc) return rc;
+// Feedback gains and plan sensitivities with HOST doubles, arguments checked by the caller: one staging slot,
+// [dyn? | terminal_weights? | z? | K? | k_sp? | k_up? | ok] in the handle's dtype, one copy in, the kernels, one copy out, one
+// synchronisation.  gain_call: K alone through cpmpc_feedback_gain_batch (the layout is then [.. | K | ok]).
+static int sensitivities_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, bool gain_call,
+                              double* K_host, double* k_sp_host, double* k_up_host, int32_t* ok_host) {
   DeviceGuard guard(s->device);
   const size_t nB = (size_t)B, e = s->esize;
   const size_t n_dyn = in->dyn ? (size_t)s->NP * nB : 0, n_tw = in->terminal_weights ? (size_t)s->NX * nB : 0;
-  const size_t n_z = in->z ? (size_t)s->dim * nB : 0, n_K = (size_t)n_rows * (size_t)s->NX * nB;
-  const size_t off_K = (n_dyn + n_tw + n_z) * e, off_ok = off_K + n_K * e;
-  rc = ensure_slot(s, 0, off_ok + nB * sizeof(int32_t));
+  const size_t n_z = in->z ? (size_t)s->dim * nB : 0;
+  const size_t n_K = K_host ? (size_t)n_rows * (size_t)s->NX * nB : 0;
+  const size_t n_sp = k_sp_host ? (size_t)n_rows * nB : 0, n_up = k_up_host ? (size_t)n_rows * nB : 0;
+  const size_t n_out = n_K + n_sp + n_up;
+  const size_t off_K = (n_dyn + n_tw + n_z) * e, off_ok = off_K + n_out * e;
+  int rc = ensure_slot(s, 0, off_ok + nB * sizeof(int32_t));
   if (rc) return rc;
   HostSlot& sl = s->slot[0];
   auto to_mirror = [&](const void* src, size_t first, size_t n) {
@@ -367,22 +369,48 @@ extern "C" int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const 
   di.dyn = n_dyn ? d_base : nullptr;
   di.terminal_weights = n_tw ? d_base + n_dyn * e : nullptr;
   di.z = n_z ? d_base + (n_dyn + n_tw) * e : nullptr;
-  rc = cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_base + off_K, (int32_t*)(d_base + off_ok), sl.stream);
+  void* const d_K = n_K ? d_base + off_K : nullptr;
+  void* const d_sp = n_sp ? d_base + off_K + n_K * e : nullptr;
+  void* const d_up = n_up ? d_base + off_K + (n_K + n_sp) * e : nullptr;
+  int32_t* const d_ok = (int32_t*)(d_base + off_ok);
+  rc = gain_call ? cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_K, d_ok, sl.stream)
+                 : cpmpc_plan_sensitivity_batch(s, B, &di, n_rows, d_K, d_sp, d_up, d_ok, sl.stream);
   hipError_t e1 = hipSuccess;
   if (rc == CPMPC_OK)
-    e1 = hipMemcpyAsync((char*)sl.pin + off_K, d_base + off_K, n_K * e + nB * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream);
+    e1 = hipMemcpyAsync((char*)sl.pin + off_K, d_base + off_K, n_out * e + nB * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream);
   const hipError_t e2 = hipStreamSynchronize(sl.stream);  // also on failure: the copy in still reads the pinned mirror
   if (rc) return rc;
   if (e1 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e1));
   if (e2 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e2));
-  if (s->dtype == CPMPC_F32) {
-    const float* h = (const float*)((const char*)sl.pin + off_K);
-    for (size_t i = 0; i < n_K; ++i) K_host[i] = (double)h[i];
-  } else {
-    memcpy(K_host, (const char*)sl.pin + off_K, n_K * 8);
-  }
+  auto from_mirror = [&](double* dst, size_t first, size_t n) {
+    if (!dst) return;
+    const char* base = (const char*)sl.pin + off_K;
+    if (s->dtype == CPMPC_F32) {
+      const float* h = (const float*)base + first;
+      for (size_t i = 0; i < n; ++i) dst[i] = (double)h[i];
+    } else {
+      memcpy(dst, (const double*)base + first, n * 8);
+    }
+  };
+  from_mirror(K_host, 0, n_K);
+  from_mirror(k_sp_host, n_K, n_sp);
+  from_mirror(k_up_host, n_K + n_sp, n_up);
   if (ok_host) memcpy(ok_host, (const char*)sl.pin + off_ok, nB * sizeof(int32_t));
   return CPMPC_OK;
+}
+
+extern "C" int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                                              double* K_host, int32_t* ok_host) {
+  const int rc = check_gain_args(s, B, in, n_rows, K_host);
+  if (rc) return rc;
+  return sensitivities_host(s, B, in, n_rows, true, K_host, nullptr, nullptr, ok_host);
+}
+
+extern "C" int cpmpc_plan_sensitivity_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                                                 double* K_host, double* k_sp_host, double* k_up_host, int32_t* ok_host) {
+  const int rc = check_gain_args(s, B, in, n_rows, K_host ? K_host : (k_sp_host ? k_sp_host : k_up_host));
+  if (rc) return rc;
+  return sensitivities_host(s, B, in, n_rows, false, K_host, k_sp_host, k_up_host, ok_host);
 }
 
 // Staging of the handle-less host-pointer plant step: per host thread and device, grown on demand and kept (a

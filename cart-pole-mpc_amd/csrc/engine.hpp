@@ -209,6 +209,12 @@ struct Engine {
   // u_out = clamp(u_nom + K0 . wrap(x - x_nom), +-u_limit), elementwise
   void (*feedback_apply)(int64_t B, const void* u_nom, const void* K0, const void* x_nom, const void* x, double u_limit,
                          void* u_out, hipStream_t stream);
+  // K, k_sp = du / dset_point, k_up = du / du_prev of the QP at z, those that are not null (plan_sensitivity_kernels.hpp):
+  // K [n_rows][NX][B], k_sp / k_up [n_rows][B], ok [B] nullable
+  void (*plan_sensitivity)(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, void* k_sp,
+                           void* k_up, int32_t* ok, hipStream_t stream);
+  // the first-order update of rows 0 .. n_rows-1 of the plan, elementwise (plan_update_kernel)
+  void (*plan_update)(int64_t B, int n_rows, const cpmpc_plan_update* u, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

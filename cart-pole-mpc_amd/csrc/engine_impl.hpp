@@ -10,6 +10,7 @@
 #include "mpc_kernels.hpp"
 #include "mpc_fused.hpp"
 #include "feedback_kernels.hpp"
+#include "plan_sensitivity_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -542,6 +543,42 @@ static void feedback_apply_impl(int64_t B, const void* u_nom, const void* K0, co
                      (const R*)u_nom, (const R*)K0, (const R*)x_nom, (const R*)x, (R)u_limit, (R*)u_out);
 }
 
+// ---- plan sensitivities ----------------------------------------------------------------------------------------------
+// feedback_gain_impl's linearisation at z, then plan_sensitivity_kernel for the outputs that are not null; the same
+// scratch is written.
+template <typename R, typename M>
+static void plan_sensitivity_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, void* k_sp,
+                                  void* k_up, int32_t* ok, hipStream_t st) {
+  SolverArgs<R, M> a;
+  fill_args<R, M>(s, B, a);
+  a.dyn = (const R*)in->dyn;
+  a.term_w_pp = (const R*)in->terminal_weights;
+  if (in->dyn == nullptr) a.consts = M::template make<double>(in->dyn_shared_host);
+  const XV<R, M::NX>* zx_in = a.zx;
+  const R* zu_in = a.zu;
+  if (in->z != nullptr) {
+    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->z,
+                       a.dzx, a.dzu);
+    zx_in = a.dzx;
+    zu_in = a.dzu;
+  }
+  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
+  if (sizeof(R) == 4 && s->wide_qp)
+    hipLaunchKernelGGL((plan_sensitivity_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, (R*)k_sp,
+                       (R*)k_up, ok);
+  else
+    hipLaunchKernelGGL((plan_sensitivity_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, (R*)k_sp,
+                       (R*)k_up, ok);
+}
+
+template <typename R, typename M>
+static void plan_update_impl(int64_t B, int n_rows, const cpmpc_plan_update* u, hipStream_t st) {
+  hipLaunchKernelGGL((plan_update_kernel<R, M>), dim3((unsigned)((B + 255) / 256), (unsigned)n_rows), dim3(256), 0, st, B,
+                     (const R*)u->u_nom, (const R*)u->K, (const R*)u->x_nom, (const R*)u->x, (const R*)u->k_sp,
+                     (const R*)u->sp_nom, (const R*)u->sp, (const R*)u->k_up, (const R*)u->u_prev_nom,
+                     (const R*)u->u_prev, (R)u->u_limit, (R*)u->u_out);
+}
+
 // debug builds: this unit's copies of the counters (every translation unit has its own __device__ variables)
 static int debug_read_impl(int which, unsigned long long* out) {
 #ifdef CPMPC_FUSED_TIMING
@@ -575,6 +612,6 @@ static int debug_read_impl(int which, unsigned long long* out) {
     static const Engine e = {&step_batch_impl<R, M>, &host_chunk_begin<R, M>, &host_chunk_end<R, M>, &pack_z_impl<R, M>, \
                              &unpack_z_impl<R, M>,   &dynamics_impl<R, M>,   &rk4_impl<R, M>,      &sim_impl<R, M>,    \
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
-                             &feedback_apply_impl<R, M>};                                                            \
+                             &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>};     \
     return &e;                                                                                                       \
   }

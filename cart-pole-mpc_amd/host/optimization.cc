@@ -141,6 +141,21 @@ std::vector<double> Optimization::FeedbackGain(const SingleCartPoleParams& dynam
   return K;  // [n_rows][4][B = 1]: row-major as it stands
 }
 
+Optimization::PlanSensitivities Optimization::PlanSensitivity(const SingleCartPoleParams& dynamics_params,
+                                                              const std::size_t n_rows) {
+  if (n_rows < 1 || n_rows > params_.window_length)
+    throw std::invalid_argument("PlanSensitivity: n_rows must be in [1, window_length]");
+  const auto dyn = dynamics_params.ToArray();
+  cpmpc_gain_inputs in{};
+  in.struct_size = sizeof in;
+  in.dyn_shared_host = dyn.data();
+  PlanSensitivities out{std::vector<double>(4 * n_rows), std::vector<double>(n_rows), std::vector<double>(n_rows)};
+  const int rc = cpmpc_plan_sensitivity_batch_host(solver_, 1, &in, static_cast<int>(n_rows), out.K.data(), out.k_sp.data(),
+                                                   out.k_up.data(), nullptr);
+  if (rc != CPMPC_OK) Throw(rc);
+  return out;
+}
+
 void Optimization::StepBatchInto(const double* states_soa, std::size_t B, const SingleCartPoleParams& dynamics_params,
                                  double b_x_set_point, double* u, double* predicted_states, std::int32_t* status,
                                  std::int32_t* iterations, double* final_cost, double* final_equality_l1) {

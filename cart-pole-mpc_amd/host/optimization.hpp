@@ -147,6 +147,15 @@ class Optimization {
   // std::invalid_argument before the first Step / SetPreviousSolution or for n_rows out of range.
   [[nodiscard]] std::vector<double> FeedbackGain(const SingleCartPoleParams& dynamics_params, std::size_t n_rows = 1);
 
+  // All three sensitivities of the last plan, rows 0 .. n_rows-1: K = du / dx0 row-major [n_rows][4] (FeedbackGain's,
+  // bitwise), k_sp = du / db_x_set_point [n_rows] and k_up = du / du_prev [n_rows] (the control applied before the plan
+  // starts) -- u(x0 + d, sp + e, u_prev + f) ~ u + K d + k_sp e + k_up f.  Of the unclamped, undamped QP at the previous
+  // solution, not of the converged solution (include/cpmpc.h: cpmpc_plan_sensitivity_batch); throws as FeedbackGain.
+  struct PlanSensitivities {
+    std::vector<double> K, k_sp, k_up;
+  };
+  [[nodiscard]] PlanSensitivities PlanSensitivity(const SingleCartPoleParams& dynamics_params, std::size_t n_rows = 1);
+
   const OptimizationParams& params() const noexcept { return params_; }
 
  private:

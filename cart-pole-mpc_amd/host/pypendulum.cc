@@ -151,6 +151,13 @@ PYBIND11_MODULE(pypendulum, m) {
       .def("set_host_chunk", &Optimization::SetHostChunk, py::arg("problems"))
       // K = du / dx0 of the last plan, rows 0 .. n_rows-1 as a flat row-major [n_rows][4] list (Optimization::FeedbackGain)
       .def("feedback_gain", &Optimization::FeedbackGain, py::arg("dynamics_params"), py::arg("n_rows") = 1)
+      // (K [n_rows][4] flat, k_sp [n_rows], k_up [n_rows]) of the last plan (Optimization::PlanSensitivity)
+      .def("plan_sensitivity",
+           [](Optimization& self, const SingleCartPoleParams& dynamics_params, std::size_t n_rows) {
+             auto r = self.PlanSensitivity(dynamics_params, n_rows);
+             return py::make_tuple(std::move(r.K), std::move(r.k_sp), std::move(r.k_up));
+           },
+           py::arg("dynamics_params"), py::arg("n_rows") = 1)
       // the handle's horizon exceeds cpmpc_max_parity_horizon() (include/cpmpc.h): a per-object status, also in solver_summary()
       .def_property_readonly("horizon_beyond_parity", &Optimization::HorizonBeyondParity);
 

@@ -510,6 +510,57 @@ int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_
 int cpmpc_feedback_apply_batch(int dtype, int model, int64_t B, const void* u_nom, const void* K0, const void* x_nom,
                                const void* x, double u_limit, void* u_out, void* stream);
 
+/* ---- sensitivities of the plan to the set-point and to u_prev, and the update of the whole plan ---- */
+/* The QP that gives K is just as linear in the other two inputs that change between two re-plans:
+ *     k_sp = du / dset_point   [N] per problem   (the b_x set-point of cpmpc_step_inputs, N/m),
+ *     k_up = du / du_prev      [N] per problem   (the control applied before the plan starts, the u_prev of the row
+ *                                                 u_derivative_cost_weight (u_0 - u_prev); dimensionless),
+ * so that, to first order,
+ *     u(x0 + dx, sp + dsp, u_prev + dup) ~ u + K dx + k_sp dsp + k_up dup.
+ * What they are: like K, sensitivities of the UNDAMPED, UNCLAMPED QP at the linearisation point z (Gauss-Newton: the
+ * second derivatives of the dynamics are not in them).  What they are NOT: derivatives of the converged NLP solution --
+ * one SQP step from z with the moved input lands where they say, a re-plan run to convergence lands near it.  k_sp acts
+ * through the b_x terminal row only (weight b_x_final_cost_weight, or the equality row); with that row's weight 0 it is 0.
+ * They depend on z, the dynamics parameters, the terminal weights and the two control-cost weights only: not on x0, the
+ * set-point's value, u_prev's value, the residuals or the defects.
+ *
+ * K [n_rows][NX][B], k_sp [n_rows][B], k_up [n_rows][B] in the handle's dtype, batch fastest; each is nullable and only
+ * those given are computed; at least one must be given.  1 <= n_rows <= N.  `in`, ok, the preconditions, the error codes,
+ * the precision split of float handles and the scratch written are those of cpmpc_feedback_gain_batch; a problem with
+ * ok = 0 gets NaN in every output.  K asked for here -- alone or with the others -- is BITWISE the K of
+ * cpmpc_feedback_gain_batch for the same handle and inputs (the kernel restates that one's arithmetic), and every output
+ * is bitwise the same whichever others are asked for with it.  Asynchronous on `stream`. */
+int cpmpc_plan_sensitivity_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K /*nullable*/,
+                                 void* k_sp /*nullable*/, void* k_up /*nullable*/, int32_t* ok /*nullable*/, void* stream);
+/* The same with HOST doubles (every pointer of `in`, K_host, k_sp_host, k_up_host, ok_host); synchronous.  Used by the
+ * C++ facade (pendulum::Optimization::PlanSensitivity). */
+int cpmpc_plan_sensitivity_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                                      double* K_host /*nullable*/, double* k_sp_host /*nullable*/,
+                                      double* k_up_host /*nullable*/, int32_t* ok_host /*nullable*/);
+/* The first-order re-plan of the whole horizon, one elementwise pass over rows k < n_rows:
+ *     u_out[k] = clamp(u_nom[k] + K[k] . wrap(x - x_nom) + k_sp[k] (sp - sp_nom) + k_up[k] (u_prev - u_prev_nom), +-u_limit).
+ * A step re-rolls every state of its initial guess from x0 and the controls, so the updated controls are a complete warm
+ * start.  Device pointers in `dtype`; a term is absent when its sensitivity is NULL, and a sensitivity given without both
+ * its nominal and its actual array is CPMPC_ERR_INVALID_ARG. */
+typedef struct cpmpc_plan_update {
+  uint64_t struct_size;   /* = sizeof(cpmpc_plan_update) */
+  const void* u_nom;      /* [n_rows][B] the plan */
+  const void* K;          /* [n_rows][NX][B], or NULL */
+  const void* x_nom;      /* [NX][B] the state the plan was made for */
+  const void* x;          /* [NX][B] the state now; the pole angles' differences are wrapped to (-pi, pi] */
+  const void* k_sp;       /* [n_rows][B], or NULL */
+  const void* sp_nom;     /* [B] the set-point the plan was made for */
+  const void* sp;         /* [B] the set-point now */
+  const void* k_up;       /* [n_rows][B], or NULL */
+  const void* u_prev_nom; /* [B] the u_prev the plan was made for */
+  const void* u_prev;     /* [B] the control actually applied before the plan starts */
+  double u_limit;         /* > 0; infinity: no clamp */
+  void* u_out;            /* [n_rows][B]; may alias u_nom */
+} cpmpc_plan_update;
+/* 1 <= n_rows <= 65535 (rows of the arrays given: the call knows no handle and no N; a row is one index of the launch
+ * grid's second dimension, hence the upper limit -- more is CPMPC_ERR_INVALID_ARG).  Asynchronous on `stream`. */
+int cpmpc_plan_update_batch(int dtype, int model, int64_t B, int n_rows, const cpmpc_plan_update* a, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------------ */
 
 enum {
