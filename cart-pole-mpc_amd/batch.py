@@ -352,6 +352,84 @@ class BatchOptimization:
             res["ok"] = ok
         return res
 
+    def plan_vjp(self, dyn, gbar, z=None, terminal_weights=None, want=("x0", "set_point", "u_prev"), want_ok=False):
+        """The reverse mode of plan_sensitivity (include/cpmpc.h: cpmpc_plan_vjp_batch): a cotangent gbar = dL/du
+        [n_rows, B] on the planned controls (rows at and beyond n_rows = gbar.shape[0] are zero) pulled back to the inputs
+        named in `want` -- a dict with
+            "x0"        [nx, B]  K^T gbar,
+            "set_point" [B]      k_sp^T gbar,
+            "u_prev"    [B]      k_up^T gbar,
+        and "ok" [B] int32 with want_ok (0: the problem's QP is not positive definite, its outputs are NaN).  K, k_sp and
+        k_up are never formed: one linearisation and one pass over it.  Gradients of the unclamped, undamped Gauss-Newton QP
+        at z, not of the converged solution; arguments as feedback_gain's.  Only what is named is computed."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in ("x0", "set_point", "u_prev") for w in want):
+            raise ValueError("want must name at least one of 'x0', 'set_point', 'u_prev'")
+        dev = torch.device("cuda", self.device)
+        if z is not None:
+            _require_cuda_tensor(z, "z", self.dtype)
+            if z.dim() != 2 or z.shape[0] != self.dim:
+                raise ValueError("z must be [dim=%d, B]" % self.dim)
+            B = int(z.shape[1])
+        else:
+            B = self.previous_solution_batch()
+            if B < 1:
+                raise ValueError("plan_vjp(z=None) needs a previous solution: step() first, or pass z")
+        _require_cuda_tensor(gbar, "gbar", self.dtype)
+        if gbar.dim() != 2 or gbar.shape[1] != B:
+            raise ValueError("gbar must be [n_rows, B=%d]" % B)
+        n_rows = int(gbar.shape[0])
+        inp = capi.GainInputs(struct_size=C.sizeof(capi.GainInputs))
+        if isinstance(dyn, torch.Tensor):
+            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
+            inp.dyn = dyn.data_ptr()
+        else:
+            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
+            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
+        if terminal_weights is not None:
+            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
+            inp.terminal_weights = terminal_weights.data_ptr()
+        inp.z = z.data_ptr() if z is not None else None
+        res = {}
+        if "x0" in want:
+            res["x0"] = torch.empty((self.nx, B), dtype=self.dtype, device=dev)
+        for name in ("set_point", "u_prev"):
+            if name in want:
+                res[name] = torch.empty((B,), dtype=self.dtype, device=dev)
+        ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
+        with torch.cuda.device(self.device):
+            capi.check(capi.load().cpmpc_plan_vjp_batch(self._h, B, C.byref(inp), n_rows, _ptr(gbar), _ptr(res.get("x0")),
+                                                        _ptr(res.get("set_point")), _ptr(res.get("u_prev")), _ptr(ok),
+                                                        _stream_ptr()))
+        if want_ok:
+            res["ok"] = ok
+        return res
+
+    def step_differentiable(self, x0, dyn, set_point=0.0, n_rows=None, terminal_weights=None, **step_kw):
+        """step() with a backward: returns (u, outputs), `outputs` what step(x0, dyn, set_point, ...) returns -- outputs.u is
+        bitwise step's -- and u = outputs.u[:n_rows] (n_rows None: all N rows) attached to the autograd graph of x0 and,
+        when it is a [B] tensor, set_point.
+
+        Which derivative: that of the LAST QP of the step -- the undamped, unclamped Gauss-Newton QP linearised at the
+        step's solution z (plan_vjp; include/cpmpc.h: cpmpc_plan_vjp_batch).  It is not the derivative of the converged NLP
+        solution, it ignores the +-u_limit / +-b_x_limit retraction, and nothing flows to dyn, terminal_weights or the
+        parameters.  Backward is one plan_vjp call on the current stream and is differentiable once only.  The forward
+        keeps its own copy of z, dyn and terminal_weights, so later steps on this handle do not change an earlier graph's
+        backward.  A problem whose QP is not positive definite (plan_vjp's ok = 0) gets gradient 0, not NaN.  The graph
+        holds this handle, whose workspace backward uses: it must stay open until backward has run (after close() backward
+        raises CpmpcError, a null handle)."""
+        n_rows = self.N if n_rows is None else int(n_rows)
+        if not 1 <= n_rows <= self.N:   # before the step: a refused call leaves the warm start where it was
+            raise ValueError("n_rows must be in [1, window_length = %d]" % self.N)
+        o = self.step(x0, dyn, set_point, terminal_weights=terminal_weights, **step_kw)
+        B = int(x0.shape[1])
+        z = self.get_solution(B)
+        dyn_kept = dyn.detach().clone() if isinstance(dyn, torch.Tensor) else [float(v) for v in dyn]
+        tw_kept = None if terminal_weights is None else terminal_weights.detach().clone()
+        sp_t = set_point if isinstance(set_point, torch.Tensor) else None
+        u = _PlanVjpFunction.apply(self, o.u, n_rows, z, dyn_kept, tw_kept, x0, sp_t)
+        return u, o
+
     # -- pipeline selection --------------------------------------------------------------------
     def set_pipeline(self, mode):
         """'auto' | 'split' | 'fused' (include/cpmpc.h: CPMPC_PIPELINE_*)."""
@@ -400,6 +478,28 @@ class BatchOptimization:
             capi.check(lib.cpmpc_profile_read(self._h, kid, C.byref(ms), C.byref(n)))
             res[lib.cpmpc_kernel_name(kid).decode()] = (ms.value, n.value)
         return res
+
+
+class _PlanVjpFunction(torch.autograd.Function):
+    """u[:n_rows] of a finished step as a function of x0 and the [B] set-point: backward is one plan_vjp call at the step's
+    own solution (BatchOptimization.step_differentiable)."""
+
+    @staticmethod
+    def forward(ctx, opt, u_all, n_rows, z, dyn, terminal_weights, x0, set_point):
+        ctx.opt, ctx.z, ctx.dyn, ctx.terminal_weights = opt, z, dyn, terminal_weights
+        return u_all[:n_rows].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gbar):
+        want = [name for name, i in (("x0", 6), ("set_point", 7)) if ctx.needs_input_grad[i]]
+        grads = {}
+        if want:
+            res = ctx.opt.plan_vjp(ctx.dyn, gbar.contiguous(), z=ctx.z, terminal_weights=ctx.terminal_weights, want=want,
+                                   want_ok=True)
+            live = res["ok"] != 0
+            grads = {name: torch.where(live, res[name], torch.zeros_like(res[name])) for name in want}
+        return None, None, None, None, None, None, grads.get("x0"), grads.get("set_point")
 
 
 def _fext(fext):

@@ -46,6 +46,7 @@ SYMBOLS = [
     "cpmpc_step_batch_host_in", "cpmpc_set_host_chunk", "cpmpc_host_register", "cpmpc_host_unregister",
     "cpmpc_feedback_gain_batch", "cpmpc_feedback_gain_batch_host", "cpmpc_feedback_apply_batch",
     "cpmpc_plan_sensitivity_batch", "cpmpc_plan_sensitivity_batch_host", "cpmpc_plan_update_batch",
+    "cpmpc_plan_vjp_batch", "cpmpc_plan_vjp_batch_host",
 ]
 
 
@@ -319,6 +320,8 @@ def load():
     L.cpmpc_plan_sensitivity_batch.argtypes = [vp, i64, C.POINTER(GainInputs), i32, vp, vp, vp, vp, vp]
     L.cpmpc_plan_sensitivity_batch_host.argtypes = [vp, i64, C.POINTER(GainInputs), i32, _dp, _dp, _dp, _ip]
     L.cpmpc_plan_update_batch.argtypes = [i32, i32, i64, i32, C.POINTER(PlanUpdate), vp]
+    L.cpmpc_plan_vjp_batch.argtypes = [vp, i64, C.POINTER(GainInputs), i32, vp, vp, vp, vp, vp, vp]
+    L.cpmpc_plan_vjp_batch_host.argtypes = [vp, i64, C.POINTER(GainInputs), i32, _dp, _dp, _dp, _dp, _ip]
     _lib = L
     return L
 

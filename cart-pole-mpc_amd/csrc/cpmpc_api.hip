@@ -866,6 +866,20 @@ extern "C" int cpmpc_plan_sensitivity_batch(cpmpc_solver* s, int64_t B, const cp
   return CPMPC_OK;
 }
 
+// g_x0 = K^T gbar, g_sp = k_sp^T gbar, g_up = k_up^T gbar (plan_vjp_kernels.hpp)
+extern "C" int cpmpc_plan_vjp_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* gbar,
+                                    void* g_x0, void* g_sp, void* g_up, int32_t* ok, void* stream) {
+  if (!gbar) return fail(CPMPC_ERR_INVALID_ARG, "null argument (gbar)");
+  // the gain call's checks, on whichever output was asked for (none: a null argument)
+  int rc = check_gain_args(s, B, in, n_rows, g_x0 ? g_x0 : (g_sp ? g_sp : g_up));
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  engine_of(s)->plan_vjp(s, B, in, n_rows, gbar, g_x0, g_sp, g_up, ok, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  track_caller_stream(s, (hipStream_t)stream);  // the workspace (warm start read, scratch written) was used on the caller's stream
+  return CPMPC_OK;
+}
+
 extern "C" int cpmpc_plan_update_batch(int dtype, int model, int64_t B, int n_rows, const cpmpc_plan_update* a,
                                        void* stream) {
   if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument");

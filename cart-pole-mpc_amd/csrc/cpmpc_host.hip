@@ -335,19 +335,28 @@ extern "C" int cpmpc_get_solution_host(cpmpc_solver* s, int64_t B, double* z_hos
   return get_sol_host_cols(s, B, z_host, B, 0);
 }
 
-// Feedback gains and plan sensitivities with HOST doubles, arguments checked by the caller: one staging slot,
-// [dyn? | terminal_weights? | z? | K? | k_sp? | k_up? | ok] in the handle's dtype, one copy in, the kernels, one copy out, one
-// synchronisation.  gain_call: K alone through cpmpc_feedback_gain_batch (the layout is then [.. | K | ok]).
-static int sensitivities_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, bool gain_call,
-                              double* K_host, double* k_sp_host, double* k_up_host, int32_t* ok_host) {
+// Feedback gains, plan sensitivities and their reverse mode with HOST doubles, arguments checked by the caller: one staging
+// slot, [dyn? | terminal_weights? | z? | gbar? | out0? | out1? | out2? | ok] in the handle's dtype, one copy in, the kernels,
+// one copy out, one synchronisation.  What the three outputs are depends on the call:
+//   kGain         cpmpc_feedback_gain_batch:    out0 = K [n_rows][NX][B]; out1, out2 and gbar absent
+//   kSensitivity  cpmpc_plan_sensitivity_batch: out0 = K [n_rows][NX][B], out1 = k_sp [n_rows][B], out2 = k_up [n_rows][B]
+//   kVjp          cpmpc_plan_vjp_batch:         gbar [n_rows][B] travels in with the inputs; out0 = g_x0 [NX][B],
+//                                               out1 = g_sp [B], out2 = g_up [B] -- one row each
+enum class HostSensCall { kGain, kSensitivity, kVjp };
+static int sensitivities_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, HostSensCall call,
+                              const double* gbar_host, double* K_host, double* k_sp_host, double* k_up_host,
+                              int32_t* ok_host) {
   DeviceGuard guard(s->device);
   const size_t nB = (size_t)B, e = s->esize;
   const size_t n_dyn = in->dyn ? (size_t)s->NP * nB : 0, n_tw = in->terminal_weights ? (size_t)s->NX * nB : 0;
   const size_t n_z = in->z ? (size_t)s->dim * nB : 0;
-  const size_t n_K = K_host ? (size_t)n_rows * (size_t)s->NX * nB : 0;
-  const size_t n_sp = k_sp_host ? (size_t)n_rows * nB : 0, n_up = k_up_host ? (size_t)n_rows * nB : 0;
+  const bool vjp = call == HostSensCall::kVjp;
+  const size_t n_gb = vjp ? (size_t)n_rows * nB : 0;
+  const size_t out_rows = vjp ? 1 : (size_t)n_rows;
+  const size_t n_K = K_host ? out_rows * (size_t)s->NX * nB : 0;
+  const size_t n_sp = k_sp_host ? out_rows * nB : 0, n_up = k_up_host ? out_rows * nB : 0;
   const size_t n_out = n_K + n_sp + n_up;
-  const size_t off_K = (n_dyn + n_tw + n_z) * e, off_ok = off_K + n_out * e;
+  const size_t off_K = (n_dyn + n_tw + n_z + n_gb) * e, off_ok = off_K + n_out * e;
   int rc = ensure_slot(s, 0, off_ok + nB * sizeof(int32_t));
   if (rc) return rc;
   HostSlot& sl = s->slot[0];
@@ -363,6 +372,7 @@ static int sensitivities_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_input
   if (n_dyn) to_mirror(in->dyn, 0, n_dyn);
   if (n_tw) to_mirror(in->terminal_weights, n_dyn, n_tw);
   if (n_z) to_mirror(in->z, n_dyn + n_tw, n_z);
+  if (n_gb) to_mirror(gbar_host, n_dyn + n_tw + n_z, n_gb);
   if (off_K) HIP_TRY(hipMemcpyAsync(sl.dev, sl.pin, off_K, hipMemcpyHostToDevice, sl.stream));
   char* d_base = (char*)sl.dev;
   cpmpc_gain_inputs di = *in;
@@ -373,8 +383,17 @@ static int sensitivities_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_input
   void* const d_sp = n_sp ? d_base + off_K + n_K * e : nullptr;
   void* const d_up = n_up ? d_base + off_K + (n_K + n_sp) * e : nullptr;
   int32_t* const d_ok = (int32_t*)(d_base + off_ok);
-  rc = gain_call ? cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_K, d_ok, sl.stream)
-                 : cpmpc_plan_sensitivity_batch(s, B, &di, n_rows, d_K, d_sp, d_up, d_ok, sl.stream);
+  switch (call) {
+    case HostSensCall::kGain:
+      rc = cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_K, d_ok, sl.stream);
+      break;
+    case HostSensCall::kSensitivity:
+      rc = cpmpc_plan_sensitivity_batch(s, B, &di, n_rows, d_K, d_sp, d_up, d_ok, sl.stream);
+      break;
+    case HostSensCall::kVjp:
+      rc = cpmpc_plan_vjp_batch(s, B, &di, n_rows, d_base + (n_dyn + n_tw + n_z) * e, d_K, d_sp, d_up, d_ok, sl.stream);
+      break;
+  }
   hipError_t e1 = hipSuccess;
   if (rc == CPMPC_OK)
     e1 = hipMemcpyAsync((char*)sl.pin + off_K, d_base + off_K, n_out * e + nB * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream);
@@ -403,14 +422,23 @@ extern "C" int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const 
                                               double* K_host, int32_t* ok_host) {
   const int rc = check_gain_args(s, B, in, n_rows, K_host);
   if (rc) return rc;
-  return sensitivities_host(s, B, in, n_rows, true, K_host, nullptr, nullptr, ok_host);
+  return sensitivities_host(s, B, in, n_rows, HostSensCall::kGain, nullptr, K_host, nullptr, nullptr, ok_host);
 }
 
 extern "C" int cpmpc_plan_sensitivity_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
                                                  double* K_host, double* k_sp_host, double* k_up_host, int32_t* ok_host) {
   const int rc = check_gain_args(s, B, in, n_rows, K_host ? K_host : (k_sp_host ? k_sp_host : k_up_host));
   if (rc) return rc;
-  return sensitivities_host(s, B, in, n_rows, false, K_host, k_sp_host, k_up_host, ok_host);
+  return sensitivities_host(s, B, in, n_rows, HostSensCall::kSensitivity, nullptr, K_host, k_sp_host, k_up_host, ok_host);
+}
+
+extern "C" int cpmpc_plan_vjp_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                                         const double* gbar_host, double* g_x0_host, double* g_sp_host, double* g_up_host,
+                                         int32_t* ok_host) {
+  if (!gbar_host) return fail(CPMPC_ERR_INVALID_ARG, "null argument (gbar)");
+  const int rc = check_gain_args(s, B, in, n_rows, g_x0_host ? g_x0_host : (g_sp_host ? g_sp_host : g_up_host));
+  if (rc) return rc;
+  return sensitivities_host(s, B, in, n_rows, HostSensCall::kVjp, gbar_host, g_x0_host, g_sp_host, g_up_host, ok_host);
 }
 
 // Staging of the handle-less host-pointer plant step: per host thread and device, grown on demand and kept (a

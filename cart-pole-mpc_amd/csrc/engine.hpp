@@ -215,6 +215,10 @@ struct Engine {
                            void* k_up, int32_t* ok, hipStream_t stream);
   // the first-order update of rows 0 .. n_rows-1 of the plan, elementwise (plan_update_kernel)
   void (*plan_update)(int64_t B, int n_rows, const cpmpc_plan_update* u, hipStream_t stream);
+  // g_x0 = K^T gbar [NX][B], g_sp = k_sp^T gbar [B], g_up = k_up^T gbar [B] of the QP at z, those that are not null, for
+  // the cotangent gbar [n_rows][B] (plan_vjp_kernels.hpp); ok [B] nullable.  Writes the linearisation scratch only
+  void (*plan_vjp)(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* gbar, void* g_x0,
+                   void* g_sp, void* g_up, int32_t* ok, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -11,6 +11,7 @@
 #include "mpc_fused.hpp"
 #include "feedback_kernels.hpp"
 #include "plan_sensitivity_kernels.hpp"
+#include "plan_vjp_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -579,6 +580,34 @@ static void plan_update_impl(int64_t B, int n_rows, const cpmpc_plan_update* u, 
                      (const R*)u->u_prev, (R)u->u_limit, (R*)u->u_out);
 }
 
+// ---- reverse-mode plan sensitivities ---------------------------------------------------------------------------------
+// plan_sensitivity_impl's linearisation at z, then plan_vjp_kernel for the outputs that are not null.  Only the
+// linearisation scratch (Phi, Gamma, cs) is written: the kernel itself writes no workspace array.
+template <typename R, typename M>
+static void plan_vjp_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* gbar, void* g_x0,
+                          void* g_sp, void* g_up, int32_t* ok, hipStream_t st) {
+  SolverArgs<R, M> a;
+  fill_args<R, M>(s, B, a);
+  a.dyn = (const R*)in->dyn;
+  a.term_w_pp = (const R*)in->terminal_weights;
+  if (in->dyn == nullptr) a.consts = M::template make<double>(in->dyn_shared_host);
+  const XV<R, M::NX>* zx_in = a.zx;
+  const R* zu_in = a.zu;
+  if (in->z != nullptr) {
+    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->z,
+                       a.dzx, a.dzu);
+    zx_in = a.dzx;
+    zu_in = a.dzu;
+  }
+  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
+  if (sizeof(R) == 4 && s->wide_qp)
+    hipLaunchKernelGGL((plan_vjp_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, n_rows, (const R*)gbar, (R*)g_x0,
+                       (R*)g_sp, (R*)g_up, ok);
+  else
+    hipLaunchKernelGGL((plan_vjp_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, n_rows, (const R*)gbar, (R*)g_x0,
+                       (R*)g_sp, (R*)g_up, ok);
+}
+
 // debug builds: this unit's copies of the counters (every translation unit has its own __device__ variables)
 static int debug_read_impl(int which, unsigned long long* out) {
 #ifdef CPMPC_FUSED_TIMING
@@ -612,6 +641,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
     static const Engine e = {&step_batch_impl<R, M>, &host_chunk_begin<R, M>, &host_chunk_end<R, M>, &pack_z_impl<R, M>, \
                              &unpack_z_impl<R, M>,   &dynamics_impl<R, M>,   &rk4_impl<R, M>,      &sim_impl<R, M>,    \
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
-                             &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>};     \
+                             &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
+                             &plan_vjp_impl<R, M>};                                                                  \
     return &e;                                                                                                       \
   }

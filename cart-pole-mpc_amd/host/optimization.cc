@@ -156,6 +156,21 @@ Optimization::PlanSensitivities Optimization::PlanSensitivity(const SingleCartPo
   return out;
 }
 
+Optimization::PlanGradients Optimization::PlanVjp(const SingleCartPoleParams& dynamics_params,
+                                                  const std::vector<double>& gbar) {
+  if (gbar.empty() || gbar.size() > params_.window_length)
+    throw std::invalid_argument("PlanVjp: gbar must hold between 1 and window_length rows");
+  const auto dyn = dynamics_params.ToArray();
+  cpmpc_gain_inputs in{};
+  in.struct_size = sizeof in;
+  in.dyn_shared_host = dyn.data();
+  PlanGradients out{std::vector<double>(4), 0.0, 0.0};
+  const int rc = cpmpc_plan_vjp_batch_host(solver_, 1, &in, static_cast<int>(gbar.size()), gbar.data(), out.g_x0.data(),
+                                           &out.g_sp, &out.g_up, nullptr);
+  if (rc != CPMPC_OK) Throw(rc);
+  return out;
+}
+
 void Optimization::StepBatchInto(const double* states_soa, std::size_t B, const SingleCartPoleParams& dynamics_params,
                                  double b_x_set_point, double* u, double* predicted_states, std::int32_t* status,
                                  std::int32_t* iterations, double* final_cost, double* final_equality_l1) {

@@ -156,6 +156,17 @@ class Optimization {
   };
   [[nodiscard]] PlanSensitivities PlanSensitivity(const SingleCartPoleParams& dynamics_params, std::size_t n_rows = 1);
 
+  // The reverse mode of PlanSensitivity: a cotangent gbar = dL/du on rows 0 .. gbar.size()-1 of the last plan
+  // (1 <= gbar.size() <= window_length; later rows are zero) pulled back to the three inputs -- g_x0 = K^T gbar [4],
+  // g_sp = k_sp^T gbar and g_up = k_up^T gbar -- without K, k_sp or k_up being formed.  Gradients of the unclamped,
+  // undamped Gauss-Newton QP at the previous solution, not of the converged solution (include/cpmpc.h:
+  // cpmpc_plan_vjp_batch); throws as PlanSensitivity.
+  struct PlanGradients {
+    std::vector<double> g_x0;
+    double g_sp, g_up;
+  };
+  [[nodiscard]] PlanGradients PlanVjp(const SingleCartPoleParams& dynamics_params, const std::vector<double>& gbar);
+
   const OptimizationParams& params() const noexcept { return params_; }
 
  private:

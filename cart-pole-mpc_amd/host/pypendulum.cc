@@ -158,6 +158,13 @@ PYBIND11_MODULE(pypendulum, m) {
              return py::make_tuple(std::move(r.K), std::move(r.k_sp), std::move(r.k_up));
            },
            py::arg("dynamics_params"), py::arg("n_rows") = 1)
+      // (g_x0 [4], g_sp, g_up) for a cotangent gbar on the leading rows of the last plan (Optimization::PlanVjp)
+      .def("plan_vjp",
+           [](Optimization& self, const SingleCartPoleParams& dynamics_params, const std::vector<double>& gbar) {
+             auto r = self.PlanVjp(dynamics_params, gbar);
+             return py::make_tuple(std::move(r.g_x0), r.g_sp, r.g_up);
+           },
+           py::arg("dynamics_params"), py::arg("gbar"))
       // the handle's horizon exceeds cpmpc_max_parity_horizon() (include/cpmpc.h): a per-object status, also in solver_summary()
       .def_property_readonly("horizon_beyond_parity", &Optimization::HorizonBeyondParity);
 

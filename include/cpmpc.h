@@ -537,6 +537,39 @@ int cpmpc_plan_sensitivity_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_in
 int cpmpc_plan_sensitivity_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
                                       double* K_host /*nullable*/, double* k_sp_host /*nullable*/,
                                       double* k_up_host /*nullable*/, int32_t* ok_host /*nullable*/);
+/* ---- reverse mode: a cotangent on the planned controls pulled back to x0, the set-point and u_prev ---- */
+/* For a caller who differentiates through the controller -- a cost shaped on the planned controls, a policy that feeds x0
+ * or the set-point, a state estimator upstream: given gbar = dL/du [n_rows] per problem (rows at and beyond n_rows are
+ * zero), the vector-Jacobian products
+ *     g_x0 = K^T gbar     [NX] per problem   = - Psi_0^T q,
+ *     g_sp = k_sp^T gbar  scalar             =   Rw[0] q_0,
+ *     g_up = k_up^T gbar  scalar             =   (w_du^2 / d_0) (eta_0 - w_0 . q),
+ * with  eta_k = gbar_k - upsilon_k eta_{k+1}  and  a = sum_k w_k eta_k / d_k  carried through the one descending sweep that
+ * builds S, and  q = (S + Dg)^-1 a  (notation: DESIGN.md section 5d).  K, k_sp and k_up are never formed: one
+ * linearisation, one pass over Phi and Gamma, one terminal solve, whatever n_rows is.
+ * What the gradients are: those of the UNDAMPED, UNCLAMPED Gauss-Newton QP at the linearisation point z, exactly the
+ * transposes of what cpmpc_plan_sensitivity_batch returns.  What they are NOT: derivatives of the converged NLP solution,
+ * of a clamped control, or with respect to the dynamics parameters, the weights or z.  They do not depend on x0, the
+ * set-point's value, u_prev's value, the residuals or the defects.
+ *
+ * gbar [n_rows][B], g_x0 [NX][B], g_sp [B], g_up [B] in the handle's dtype, batch fastest; each output is nullable and
+ * only those given are computed; at least one must be given, gbar must be given, 1 <= n_rows <= N.  `in`, ok, the
+ * preconditions and the error codes are those of cpmpc_plan_sensitivity_batch; a problem with ok = 0 gets NaN in every
+ * output.  Float handles carry eta, a, q and the three products in double; with cpmpc_wide_qp() Psi and w_k as well.
+ * Every output is bitwise the same whichever others are asked for with it, and n_rows < N gives bitwise what n_rows = N
+ * gives for gbar padded with zeros.  Asynchronous on `stream`; the call writes only the linearisation scratch of the
+ * workspace (Phi, Gamma, the defects; a z given in `in` goes through the step buffers), which every step recomputes before
+ * it reads it: a step's results do not depend on calls made in between. */
+int cpmpc_plan_vjp_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                         const void* gbar /* [n_rows][B] */, void* g_x0 /* [NX][B], nullable */,
+                         void* g_sp /* [B], nullable */, void* g_up /* [B], nullable */, int32_t* ok /* nullable */,
+                         void* stream);
+/* The same with HOST doubles (every pointer of `in`, gbar_host, g_x0_host, g_sp_host, g_up_host, ok_host); synchronous.
+ * Used by the C++ facade (pendulum::Optimization::PlanVjp). */
+int cpmpc_plan_vjp_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
+                              const double* gbar_host /* [n_rows][B] */, double* g_x0_host /* nullable */,
+                              double* g_sp_host /* nullable */, double* g_up_host /* nullable */,
+                              int32_t* ok_host /* nullable */);
 /* The first-order re-plan of the whole horizon, one elementwise pass over rows k < n_rows:
  *     u_out[k] = clamp(u_nom[k] + K[k] . wrap(x - x_nom) + k_sp[k] (sp - sp_nom) + k_up[k] (u_prev - u_prev_nom), +-u_limit).
  * A step re-rolls every state of its initial guess from x0 and the controls, so the updated controls are a complete warm
