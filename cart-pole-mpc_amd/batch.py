@@ -405,7 +405,81 @@ class BatchOptimization:
             res["ok"] = ok
         return res
 
-    def step_differentiable(self, x0, dyn, set_point=0.0, n_rows=None, terminal_weights=None, **step_kw):
+    def plan_weight_vjp(self, x0, dyn, gbar, set_point=0.0, u_prev=None, z=None, terminal_weights=None,
+                        want=("terminal", "u", "du_dt"), want_du=False, want_ok=False):
+        """The gradients of a loss on the planned controls with respect to the cost weights (include/cpmpc.h:
+        cpmpc_plan_weight_vjp_batch): for a cotangent gbar = dL/du+ [n_rows, B] on the controls u+ = u + du of the QP at z
+        (rows at and beyond n_rows = gbar.shape[0] are zero), a dict with the entries named in `want`,
+            "terminal" [nx, B]  dL/d(terminal weights), state order; exactly 0 for an equality row and a zero weight,
+            "u"        [B]      dL/d(u_cost_weight),
+            "du_dt"    [B]      dL/d(u_derivative_cost_weight),
+        "du" [n_rows, B] with want_du -- the primal step of that QP, one undamped SQP step without a line search -- and "ok"
+        [B] int32 with want_ok (0: the problem's QP is not positive definite, its outputs are NaN).  x0 [nx, B], set_point
+        (a float or [B]) and u_prev ([B]; None: 0) are what a step from z would see: unlike plan_vjp's, these gradients
+        depend on them.  Gradients of the unclamped, undamped Gauss-Newton QP at z, not through the line search, the clamps
+        or earlier iterations; none with respect to the dynamics parameters.  dyn, z, terminal_weights as feedback_gain's.
+        want may be empty when want_du is set (gbar is then only read for its shape and may be None with n_rows = N)."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if any(w not in ("terminal", "u", "du_dt") for w in want) or not (want or want_du):
+            raise ValueError("want must name some of 'terminal', 'u', 'du_dt' (or nothing, with want_du)")
+        dev = torch.device("cuda", self.device)
+        _require_cuda_tensor(x0, "x0", self.dtype)
+        if x0.dim() != 2 or x0.shape[0] != self.nx:
+            raise ValueError("x0 must be [%d, B]" % self.nx)
+        B = int(x0.shape[1])
+        if z is not None:
+            _require_cuda_tensor(z, "z", self.dtype, (self.dim, B))
+        elif self.previous_solution_batch() < B:
+            raise ValueError("plan_weight_vjp(z=None) needs a previous solution for every problem: step() first, or pass z")
+        if gbar is None:
+            if want:
+                raise ValueError("gbar may be None only when du is the only output")
+            n_rows = self.N
+        else:
+            _require_cuda_tensor(gbar, "gbar", self.dtype)
+            if gbar.dim() != 2 or gbar.shape[1] != B:
+                raise ValueError("gbar must be [n_rows, B=%d]" % B)
+            n_rows = int(gbar.shape[0])
+        inp = capi.WeightVjpInputs(struct_size=C.sizeof(capi.WeightVjpInputs))
+        inp.lin.struct_size = C.sizeof(capi.GainInputs)
+        if isinstance(dyn, torch.Tensor):
+            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
+            inp.lin.dyn = dyn.data_ptr()
+        else:
+            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
+            inp.lin.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
+        if terminal_weights is not None:
+            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
+            inp.lin.terminal_weights = terminal_weights.data_ptr()
+        inp.lin.z = z.data_ptr() if z is not None else None
+        inp.x0 = x0.data_ptr()
+        if isinstance(set_point, torch.Tensor):
+            _require_cuda_tensor(set_point, "set_point", self.dtype, (B,))
+            inp.set_point = set_point.data_ptr()
+        else:
+            inp.set_point_shared = float(set_point)
+        if u_prev is not None:
+            _require_cuda_tensor(u_prev, "u_prev", self.dtype, (B,))
+            inp.u_prev = u_prev.data_ptr()
+        res = {}
+        if "terminal" in want:
+            res["terminal"] = torch.empty((self.nx, B), dtype=self.dtype, device=dev)
+        for name in ("u", "du_dt"):
+            if name in want:
+                res[name] = torch.empty((B,), dtype=self.dtype, device=dev)
+        if want_du:
+            res["du"] = torch.empty((n_rows, B), dtype=self.dtype, device=dev)
+        ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
+        with torch.cuda.device(self.device):
+            capi.check(capi.load().cpmpc_plan_weight_vjp_batch(self._h, B, C.byref(inp), n_rows, _ptr(gbar),
+                                                               _ptr(res.get("terminal")), _ptr(res.get("u")),
+                                                               _ptr(res.get("du_dt")), _ptr(res.get("du")), _ptr(ok),
+                                                               _stream_ptr()))
+        if want_ok:
+            res["ok"] = ok
+        return res
+
+    def step_differentiable(self, x0, dyn, set_point=0.0, n_rows=None, terminal_weights=None, weight_grad=False, **step_kw):
         """step() with a backward: returns (u, outputs), `outputs` what step(x0, dyn, set_point, ...) returns -- outputs.u is
         bitwise step's -- and u = outputs.u[:n_rows] (n_rows None: all N rows) attached to the autograd graph of x0 and,
         when it is a [B] tensor, set_point.
@@ -417,17 +491,41 @@ class BatchOptimization:
         keeps its own copy of z, dyn and terminal_weights, so later steps on this handle do not change an earlier graph's
         backward.  A problem whose QP is not positive definite (plan_vjp's ok = 0) gets gradient 0, not NaN.  The graph
         holds this handle, whose workspace backward uses: it must stay open until backward has run (after close() backward
-        raises CpmpcError, a null handle)."""
+        raises CpmpcError, a null handle).
+
+        weight_grad=True (with a terminal_weights tensor that requires grad): backward makes one further call,
+        plan_weight_vjp at the step's z, x0, set-point and the u_prev the step's row w_du (u_0 - u_prev) saw -- control 0 of
+        the previous solution for a problem that had one, 0 for a cold start -- and returns its "terminal" gradient for
+        terminal_weights (0 for a lane with ok = 0).  u_cost_weight and u_derivative_cost_weight are parameters of the
+        handle, not tensors: their gradients are available from plan_weight_vjp only.  With weight_grad=False this is the
+        function it was before the argument existed, graph included."""
         n_rows = self.N if n_rows is None else int(n_rows)
         if not 1 <= n_rows <= self.N:   # before the step: a refused call leaves the warm start where it was
             raise ValueError("n_rows must be in [1, window_length = %d]" % self.N)
+        if weight_grad and not isinstance(terminal_weights, torch.Tensor):
+            raise ValueError("weight_grad=True needs a terminal_weights tensor")
+        u_prev = None
+        if weight_grad:   # what prepare_kernel reads before the previous solution is overwritten (optimization.cc:288-291)
+            _require_cuda_tensor(x0, "x0", self.dtype)
+            if x0.dim() != 2 or x0.shape[0] != self.nx:
+                raise ValueError("x0 must be [%d, B]" % self.nx)
+            B = int(x0.shape[1])
+            warm = min(self.previous_solution_batch(), B)
+            u_prev = torch.zeros((B,), dtype=self.dtype, device=torch.device("cuda", self.device))
+            if warm > 0:   # (the C-ABI reads a solution whole: one [dim, warm] copy, of which row nx S is control 0)
+                u_prev[:warm] = self.get_solution(warm)[self.nx * self.S]
         o = self.step(x0, dyn, set_point, terminal_weights=terminal_weights, **step_kw)
         B = int(x0.shape[1])
         z = self.get_solution(B)
         dyn_kept = dyn.detach().clone() if isinstance(dyn, torch.Tensor) else [float(v) for v in dyn]
         tw_kept = None if terminal_weights is None else terminal_weights.detach().clone()
         sp_t = set_point if isinstance(set_point, torch.Tensor) else None
-        u = _PlanVjpFunction.apply(self, o.u, n_rows, z, dyn_kept, tw_kept, x0, sp_t)
+        if weight_grad:
+            sp_kept = set_point.detach().clone() if sp_t is not None else float(set_point)
+            u = _PlanWeightVjpFunction.apply(self, o.u, n_rows, z, dyn_kept, tw_kept, x0.detach().clone(), sp_kept, u_prev,
+                                             x0, sp_t, terminal_weights)
+        else:
+            u = _PlanVjpFunction.apply(self, o.u, n_rows, z, dyn_kept, tw_kept, x0, sp_t)
         return u, o
 
     # -- pipeline selection --------------------------------------------------------------------
@@ -500,6 +598,34 @@ class _PlanVjpFunction(torch.autograd.Function):
             live = res["ok"] != 0
             grads = {name: torch.where(live, res[name], torch.zeros_like(res[name])) for name in want}
         return None, None, None, None, None, None, grads.get("x0"), grads.get("set_point")
+
+
+class _PlanWeightVjpFunction(torch.autograd.Function):
+    """_PlanVjpFunction with terminal_weights as a third differentiable input: backward adds one plan_weight_vjp call at the
+    step's z, x0, set-point and u_prev (BatchOptimization.step_differentiable(weight_grad=True))."""
+
+    @staticmethod
+    def forward(ctx, opt, u_all, n_rows, z, dyn, tw_kept, x0_kept, sp_kept, u_prev, x0, set_point, terminal_weights):
+        ctx.opt, ctx.z, ctx.dyn, ctx.terminal_weights = opt, z, dyn, tw_kept
+        ctx.x0, ctx.set_point, ctx.u_prev = x0_kept, sp_kept, u_prev
+        return u_all[:n_rows].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gbar):
+        gbar = gbar.contiguous()
+        want = [name for name, i in (("x0", 9), ("set_point", 10)) if ctx.needs_input_grad[i]]
+        grads = {}
+        if want:
+            res = ctx.opt.plan_vjp(ctx.dyn, gbar, z=ctx.z, terminal_weights=ctx.terminal_weights, want=want, want_ok=True)
+            live = res["ok"] != 0
+            grads = {name: torch.where(live, res[name], torch.zeros_like(res[name])) for name in want}
+        g_tw = None
+        if ctx.needs_input_grad[11]:
+            res = ctx.opt.plan_weight_vjp(ctx.x0, ctx.dyn, gbar, set_point=ctx.set_point, u_prev=ctx.u_prev, z=ctx.z,
+                                          terminal_weights=ctx.terminal_weights, want=("terminal",), want_ok=True)
+            g_tw = torch.where(res["ok"] != 0, res["terminal"], torch.zeros_like(res["terminal"]))
+        return None, None, None, None, None, None, None, None, None, grads.get("x0"), grads.get("set_point"), g_tw
 
 
 def _fext(fext):

@@ -47,6 +47,7 @@ SYMBOLS = [
     "cpmpc_feedback_gain_batch", "cpmpc_feedback_gain_batch_host", "cpmpc_feedback_apply_batch",
     "cpmpc_plan_sensitivity_batch", "cpmpc_plan_sensitivity_batch_host", "cpmpc_plan_update_batch",
     "cpmpc_plan_vjp_batch", "cpmpc_plan_vjp_batch_host",
+    "cpmpc_plan_weight_vjp_batch", "cpmpc_plan_weight_vjp_batch_host",
 ]
 
 
@@ -176,6 +177,20 @@ class GainInputs(C.Structure):
         ("dyn", C.c_void_p),
         ("terminal_weights", C.c_void_p),
         ("z", C.c_void_p),
+    ]
+
+
+class WeightVjpInputs(C.Structure):
+    """cpmpc_weight_vjp_inputs: `lin` as cpmpc_plan_vjp_batch's inputs, and what the primal QP solve needs beside them -- x0
+    (required), the set-point (shared, or per problem) and u_prev (NULL: 0); device pointers
+    (cpmpc_plan_weight_vjp_batch) or HOST doubles (..._host)."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("lin", GainInputs),
+        ("x0", C.c_void_p),
+        ("set_point_shared", C.c_double),
+        ("set_point", C.c_void_p),
+        ("u_prev", C.c_void_p),
     ]
 
 
@@ -322,6 +337,8 @@ def load():
     L.cpmpc_plan_update_batch.argtypes = [i32, i32, i64, i32, C.POINTER(PlanUpdate), vp]
     L.cpmpc_plan_vjp_batch.argtypes = [vp, i64, C.POINTER(GainInputs), i32, vp, vp, vp, vp, vp, vp]
     L.cpmpc_plan_vjp_batch_host.argtypes = [vp, i64, C.POINTER(GainInputs), i32, _dp, _dp, _dp, _dp, _ip]
+    L.cpmpc_plan_weight_vjp_batch.argtypes = [vp, i64, C.POINTER(WeightVjpInputs), i32, vp, vp, vp, vp, vp, vp, vp]
+    L.cpmpc_plan_weight_vjp_batch_host.argtypes = [vp, i64, C.POINTER(WeightVjpInputs), i32, _dp, _dp, _dp, _dp, _dp, _ip]
     _lib = L
     return L
 

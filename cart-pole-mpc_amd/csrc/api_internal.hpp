@@ -26,6 +26,10 @@ CPMPC_HIDDEN bool device_is_gfx950(int dev);
 CPMPC_HIDDEN int current_device_ok();
 // the argument checks of cpmpc_feedback_gain_batch[_host] (no device needed)
 CPMPC_HIDDEN int check_gain_args(const cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* K);
+// the argument checks of cpmpc_plan_weight_vjp_batch[_host] (no device needed unless the handle is null)
+CPMPC_HIDDEN int check_weight_vjp_args(const cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows,
+                                       const void* gbar, const void* g_tw, const void* g_wu, const void* g_wdu,
+                                       const void* du);
 
 // (cpmpc_host.hip) Grows the device buffer *dev -- and its pinned host mirror *pin when `pin` is given -- to at least
 // `bytes` (*cap: their size); never shrinks, allocates at least 4 096 bytes.  `stream` is synchronised before the old

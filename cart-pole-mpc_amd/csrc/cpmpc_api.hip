@@ -880,6 +880,40 @@ extern "C" int cpmpc_plan_vjp_batch(cpmpc_solver* s, int64_t B, const cpmpc_gain
   return CPMPC_OK;
 }
 
+// The argument checks of cpmpc_plan_weight_vjp_batch[_host], the ones that need no handle first.  A null handle with
+// otherwise well-formed arguments is CPMPC_ERR_NO_DEVICE where no usable device is visible (no handle can exist there: the
+// product has no CPU path), CPMPC_ERR_INVALID_ARG otherwise.
+int check_weight_vjp_args(const cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows, const void* gbar,
+                          const void* g_tw, const void* g_wu, const void* g_wdu, const void* du) {
+  if (!in) return fail(CPMPC_ERR_INVALID_ARG, "null argument (in)");
+  if (in->struct_size != sizeof(cpmpc_weight_vjp_inputs))
+    return fail(CPMPC_ERR_INVALID_ARG,
+                "cpmpc_weight_vjp_inputs.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_weight_vjp_inputs))",
+                (unsigned long long)in->struct_size, sizeof(cpmpc_weight_vjp_inputs));
+  if (!g_tw && !g_wu && !g_wdu && !du) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (n_rows < 1) return fail(CPMPC_ERR_INVALID_ARG, "n_rows must be >= 1");
+  if (!in->x0) return fail(CPMPC_ERR_INVALID_ARG, "null argument (x0)");
+  if (!gbar && (g_tw || g_wu || g_wdu)) return fail(CPMPC_ERR_INVALID_ARG, "null argument (gbar, with a gradient output)");
+  if (!s) {
+    const int rc = current_device_ok();
+    return rc ? rc : fail(CPMPC_ERR_INVALID_ARG, "null argument (handle)");
+  }
+  return check_gain_args(s, B, &in->lin, n_rows, in);
+}
+
+// g_tw, g_wu, g_wdu = d(gbar . u+)/d(cost weights) and the primal QP step du (plan_weight_vjp_kernels.hpp)
+extern "C" int cpmpc_plan_weight_vjp_batch(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows,
+                                           const void* gbar, void* g_tw, void* g_wu, void* g_wdu, void* du, int32_t* ok,
+                                           void* stream) {
+  int rc = check_weight_vjp_args(s, B, in, n_rows, gbar, g_tw, g_wu, g_wdu, du);
+  if (rc) return rc;
+  DeviceGuard guard(s->device);
+  engine_of(s)->plan_weight_vjp(s, B, in, n_rows, gbar, g_tw, g_wu, g_wdu, du, ok, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  track_caller_stream(s, (hipStream_t)stream);  // the workspace (warm start read, scratch written) was used on the caller's stream
+  return CPMPC_OK;
+}
+
 extern "C" int cpmpc_plan_update_batch(int dtype, int model, int64_t B, int n_rows, const cpmpc_plan_update* a,
                                        void* stream) {
   if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument");

@@ -335,9 +335,69 @@ extern "C" int cpmpc_get_solution_host(cpmpc_solver* s, int64_t B, double* z_hos
   return get_sol_host_cols(s, B, z_host, B, 0);
 }
 
-// Feedback gains, plan sensitivities and their reverse mode with HOST doubles, arguments checked by the caller: one staging
-// slot, [dyn? | terminal_weights? | z? | gbar? | out0? | out1? | out2? | ok] in the handle's dtype, one copy in, the kernels,
-// one copy out, one synchronisation.  What the three outputs are depends on the call:
+// One call of the sensitivity family with HOST doubles, arguments checked by the caller: one staging slot,
+// [the inputs that are given, in order | the outputs that are asked for, in order | ok] in the handle's dtype, one copy in,
+// `launch` on the slot's stream with the device addresses (NULL where the host pointer is), one copy out, one
+// synchronisation -- also when `launch` fails: the copy in still reads the pinned mirror.
+template <int NI, int NO, typename Launch>
+static int staged_host_call(cpmpc_solver* s, int64_t B, const void* const (&src)[NI], const size_t (&n_in)[NI],
+                            double* const (&dst)[NO], const size_t (&n_out)[NO], int32_t* ok_host, Launch launch) {
+  DeviceGuard guard(s->device);
+  const size_t nB = (size_t)B, e = s->esize;
+  size_t first_in[NI], first_out[NO], n_ins = 0, n_outs = 0;
+  for (int i = 0; i < NI; ++i) {
+    first_in[i] = n_ins;
+    if (src[i]) n_ins += n_in[i];
+  }
+  for (int i = 0; i < NO; ++i) {
+    first_out[i] = n_outs;
+    if (dst[i]) n_outs += n_out[i];
+  }
+  const size_t off_out = n_ins * e, off_ok = off_out + n_outs * e;
+  int rc = ensure_slot(s, 0, off_ok + nB * sizeof(int32_t));
+  if (rc) return rc;
+  HostSlot& sl = s->slot[0];
+  for (int i = 0; i < NI; ++i) {
+    if (!src[i]) continue;
+    const double* d = (const double*)src[i];
+    if (s->dtype == CPMPC_F32) {
+      float* h = (float*)sl.pin + first_in[i];
+      for (size_t j = 0; j < n_in[i]; ++j) h[j] = (float)d[j];
+    } else {
+      memcpy((double*)sl.pin + first_in[i], d, n_in[i] * 8);
+    }
+  }
+  if (off_out) HIP_TRY(hipMemcpyAsync(sl.dev, sl.pin, off_out, hipMemcpyHostToDevice, sl.stream));
+  char* const d_base = (char*)sl.dev;
+  const void* d_in[NI];
+  void* d_o[NO];
+  for (int i = 0; i < NI; ++i) d_in[i] = src[i] ? d_base + first_in[i] * e : nullptr;
+  for (int i = 0; i < NO; ++i) d_o[i] = dst[i] ? d_base + off_out + first_out[i] * e : nullptr;
+  rc = launch(d_in, d_o, (int32_t*)(d_base + off_ok), sl.stream);
+  hipError_t e1 = hipSuccess;
+  if (rc == CPMPC_OK)
+    e1 = hipMemcpyAsync((char*)sl.pin + off_out, d_base + off_out, n_outs * e + nB * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        sl.stream);
+  const hipError_t e2 = hipStreamSynchronize(sl.stream);
+  if (rc) return rc;
+  if (e1 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e1));
+  if (e2 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e2));
+  for (int i = 0; i < NO; ++i) {
+    if (!dst[i]) continue;
+    const char* base = (const char*)sl.pin + off_out;
+    if (s->dtype == CPMPC_F32) {
+      const float* h = (const float*)base + first_out[i];
+      for (size_t j = 0; j < n_out[i]; ++j) dst[i][j] = (double)h[j];
+    } else {
+      memcpy(dst[i], (const double*)base + first_out[i], n_out[i] * 8);
+    }
+  }
+  if (ok_host) memcpy(ok_host, (const char*)sl.pin + off_ok, nB * sizeof(int32_t));
+  return CPMPC_OK;
+}
+
+// Feedback gains, plan sensitivities and their reverse mode with HOST doubles: the inputs are [dyn? | terminal_weights? | z? |
+// gbar?].  What the three outputs are depends on the call:
 //   kGain         cpmpc_feedback_gain_batch:    out0 = K [n_rows][NX][B]; out1, out2 and gbar absent
 //   kSensitivity  cpmpc_plan_sensitivity_batch: out0 = K [n_rows][NX][B], out1 = k_sp [n_rows][B], out2 = k_up [n_rows][B]
 //   kVjp          cpmpc_plan_vjp_batch:         gbar [n_rows][B] travels in with the inputs; out0 = g_x0 [NX][B],
@@ -346,76 +406,29 @@ enum class HostSensCall { kGain, kSensitivity, kVjp };
 static int sensitivities_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, HostSensCall call,
                               const double* gbar_host, double* K_host, double* k_sp_host, double* k_up_host,
                               int32_t* ok_host) {
-  DeviceGuard guard(s->device);
-  const size_t nB = (size_t)B, e = s->esize;
-  const size_t n_dyn = in->dyn ? (size_t)s->NP * nB : 0, n_tw = in->terminal_weights ? (size_t)s->NX * nB : 0;
-  const size_t n_z = in->z ? (size_t)s->dim * nB : 0;
+  const size_t nB = (size_t)B;
   const bool vjp = call == HostSensCall::kVjp;
-  const size_t n_gb = vjp ? (size_t)n_rows * nB : 0;
   const size_t out_rows = vjp ? 1 : (size_t)n_rows;
-  const size_t n_K = K_host ? out_rows * (size_t)s->NX * nB : 0;
-  const size_t n_sp = k_sp_host ? out_rows * nB : 0, n_up = k_up_host ? out_rows * nB : 0;
-  const size_t n_out = n_K + n_sp + n_up;
-  const size_t off_K = (n_dyn + n_tw + n_z + n_gb) * e, off_ok = off_K + n_out * e;
-  int rc = ensure_slot(s, 0, off_ok + nB * sizeof(int32_t));
-  if (rc) return rc;
-  HostSlot& sl = s->slot[0];
-  auto to_mirror = [&](const void* src, size_t first, size_t n) {
-    const double* d = (const double*)src;
-    if (s->dtype == CPMPC_F32) {
-      float* h = (float*)sl.pin + first;
-      for (size_t i = 0; i < n; ++i) h[i] = (float)d[i];
-    } else {
-      memcpy((double*)sl.pin + first, d, n * 8);
-    }
-  };
-  if (n_dyn) to_mirror(in->dyn, 0, n_dyn);
-  if (n_tw) to_mirror(in->terminal_weights, n_dyn, n_tw);
-  if (n_z) to_mirror(in->z, n_dyn + n_tw, n_z);
-  if (n_gb) to_mirror(gbar_host, n_dyn + n_tw + n_z, n_gb);
-  if (off_K) HIP_TRY(hipMemcpyAsync(sl.dev, sl.pin, off_K, hipMemcpyHostToDevice, sl.stream));
-  char* d_base = (char*)sl.dev;
-  cpmpc_gain_inputs di = *in;
-  di.dyn = n_dyn ? d_base : nullptr;
-  di.terminal_weights = n_tw ? d_base + n_dyn * e : nullptr;
-  di.z = n_z ? d_base + (n_dyn + n_tw) * e : nullptr;
-  void* const d_K = n_K ? d_base + off_K : nullptr;
-  void* const d_sp = n_sp ? d_base + off_K + n_K * e : nullptr;
-  void* const d_up = n_up ? d_base + off_K + (n_K + n_sp) * e : nullptr;
-  int32_t* const d_ok = (int32_t*)(d_base + off_ok);
-  switch (call) {
-    case HostSensCall::kGain:
-      rc = cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_K, d_ok, sl.stream);
-      break;
-    case HostSensCall::kSensitivity:
-      rc = cpmpc_plan_sensitivity_batch(s, B, &di, n_rows, d_K, d_sp, d_up, d_ok, sl.stream);
-      break;
-    case HostSensCall::kVjp:
-      rc = cpmpc_plan_vjp_batch(s, B, &di, n_rows, d_base + (n_dyn + n_tw + n_z) * e, d_K, d_sp, d_up, d_ok, sl.stream);
-      break;
-  }
-  hipError_t e1 = hipSuccess;
-  if (rc == CPMPC_OK)
-    e1 = hipMemcpyAsync((char*)sl.pin + off_K, d_base + off_K, n_out * e + nB * sizeof(int32_t), hipMemcpyDeviceToHost, sl.stream);
-  const hipError_t e2 = hipStreamSynchronize(sl.stream);  // also on failure: the copy in still reads the pinned mirror
-  if (rc) return rc;
-  if (e1 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e1));
-  if (e2 != hipSuccess) return fail(CPMPC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e2));
-  auto from_mirror = [&](double* dst, size_t first, size_t n) {
-    if (!dst) return;
-    const char* base = (const char*)sl.pin + off_K;
-    if (s->dtype == CPMPC_F32) {
-      const float* h = (const float*)base + first;
-      for (size_t i = 0; i < n; ++i) dst[i] = (double)h[i];
-    } else {
-      memcpy(dst, (const double*)base + first, n * 8);
-    }
-  };
-  from_mirror(K_host, 0, n_K);
-  from_mirror(k_sp_host, n_K, n_sp);
-  from_mirror(k_up_host, n_K + n_sp, n_up);
-  if (ok_host) memcpy(ok_host, (const char*)sl.pin + off_ok, nB * sizeof(int32_t));
-  return CPMPC_OK;
+  const void* const src[4] = {in->dyn, in->terminal_weights, in->z, vjp ? gbar_host : nullptr};
+  const size_t n_in[4] = {(size_t)s->NP * nB, (size_t)s->NX * nB, (size_t)s->dim * nB, (size_t)n_rows * nB};
+  double* const dst[3] = {K_host, k_sp_host, k_up_host};
+  const size_t n_out[3] = {out_rows * (size_t)s->NX * nB, out_rows * nB, out_rows * nB};
+  return staged_host_call(s, B, src, n_in, dst, n_out, ok_host,
+                          [&](const void* const* d_in, void* const* d_o, int32_t* d_ok, hipStream_t stream) {
+                            cpmpc_gain_inputs di = *in;
+                            di.dyn = d_in[0];
+                            di.terminal_weights = d_in[1];
+                            di.z = d_in[2];
+                            switch (call) {
+                              case HostSensCall::kGain:
+                                return cpmpc_feedback_gain_batch(s, B, &di, n_rows, d_o[0], d_ok, stream);
+                              case HostSensCall::kSensitivity:
+                                return cpmpc_plan_sensitivity_batch(s, B, &di, n_rows, d_o[0], d_o[1], d_o[2], d_ok, stream);
+                              case HostSensCall::kVjp:
+                                break;
+                            }
+                            return cpmpc_plan_vjp_batch(s, B, &di, n_rows, d_in[3], d_o[0], d_o[1], d_o[2], d_ok, stream);
+                          });
 }
 
 extern "C" int cpmpc_feedback_gain_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows,
@@ -439,6 +452,33 @@ extern "C" int cpmpc_plan_vjp_batch_host(cpmpc_solver* s, int64_t B, const cpmpc
   const int rc = check_gain_args(s, B, in, n_rows, g_x0_host ? g_x0_host : (g_sp_host ? g_sp_host : g_up_host));
   if (rc) return rc;
   return sensitivities_host(s, B, in, n_rows, HostSensCall::kVjp, gbar_host, g_x0_host, g_sp_host, g_up_host, ok_host);
+}
+
+// The weight gradients with HOST doubles: the inputs are [dyn? | terminal_weights? | z? | x0 | set_point? | u_prev? | gbar?], the
+// outputs [g_tw? | g_wu? | g_wdu? | du?] (staged_host_call).
+extern "C" int cpmpc_plan_weight_vjp_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows,
+                                                const double* gbar_host, double* g_tw_host, double* g_wu_host,
+                                                double* g_wdu_host, double* du_host, int32_t* ok_host) {
+  const int rc = check_weight_vjp_args(s, B, in, n_rows, gbar_host, g_tw_host, g_wu_host, g_wdu_host, du_host);
+  if (rc) return rc;
+  const size_t nB = (size_t)B;
+  const void* const src[7] = {in->lin.dyn, in->lin.terminal_weights, in->lin.z, in->x0, in->set_point, in->u_prev, gbar_host};
+  const size_t n_in[7] = {(size_t)s->NP * nB, (size_t)s->NX * nB, (size_t)s->dim * nB, (size_t)s->NX * nB, nB, nB,
+                          (size_t)n_rows * nB};
+  double* const dst[4] = {g_tw_host, g_wu_host, g_wdu_host, du_host};
+  const size_t n_out[4] = {(size_t)s->NX * nB, nB, nB, (size_t)n_rows * nB};
+  return staged_host_call(s, B, src, n_in, dst, n_out, ok_host,
+                          [&](const void* const* d_in, void* const* d_o, int32_t* d_ok, hipStream_t stream) {
+                            cpmpc_weight_vjp_inputs di = *in;
+                            di.lin.dyn = d_in[0];
+                            di.lin.terminal_weights = d_in[1];
+                            di.lin.z = d_in[2];
+                            di.x0 = d_in[3];
+                            di.set_point = d_in[4];
+                            di.u_prev = d_in[5];
+                            return cpmpc_plan_weight_vjp_batch(s, B, &di, n_rows, d_in[6], d_o[0], d_o[1], d_o[2], d_o[3], d_ok,
+                                                               stream);
+                          });
 }
 
 // Staging of the handle-less host-pointer plant step: per host thread and device, grown on demand and kept (a

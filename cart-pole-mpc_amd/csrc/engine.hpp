@@ -219,6 +219,11 @@ struct Engine {
   // the cotangent gbar [n_rows][B] (plan_vjp_kernels.hpp); ok [B] nullable.  Writes the linearisation scratch only
   void (*plan_vjp)(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* gbar, void* g_x0,
                    void* g_sp, void* g_up, int32_t* ok, hipStream_t stream);
+  // the gradients of gbar . (u + du) with respect to the cost weights, g_tw [NX][B], g_wu [B], g_wdu [B], and the primal QP
+  // step du [n_rows][B] of the QP at z, those that are not null (plan_weight_vjp_kernels.hpp); ok [B] nullable.  Writes the
+  // linearisation scratch and the rows of W and T only
+  void (*plan_weight_vjp)(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows, const void* gbar,
+                          void* g_tw, void* g_wu, void* g_wdu, void* du, int32_t* ok, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

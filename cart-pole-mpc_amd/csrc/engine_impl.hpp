@@ -12,6 +12,7 @@
 #include "feedback_kernels.hpp"
 #include "plan_sensitivity_kernels.hpp"
 #include "plan_vjp_kernels.hpp"
+#include "plan_weight_vjp_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -608,6 +609,38 @@ static void plan_vjp_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* i
                        (R*)g_sp, (R*)g_up, ok);
 }
 
+// ---- weight gradients of the plan ------------------------------------------------------------------------------------
+// plan_vjp_impl's linearisation at z, then plan_weight_vjp_kernel for the outputs that are not null, with the inputs the
+// primal solve needs (x0, the set-point, u_prev) where a step has them.  The linearisation scratch (Phi, Gamma, cs) and the
+// rows of W and T are written, nothing else.
+template <typename R, typename M>
+static void plan_weight_vjp_impl(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows, const void* gbar,
+                                 void* g_tw, void* g_wu, void* g_wdu, void* du, int32_t* ok, hipStream_t st) {
+  SolverArgs<R, M> a;
+  fill_args<R, M>(s, B, a);
+  a.x0 = (const R*)in->x0;
+  a.dyn = (const R*)in->lin.dyn;
+  a.set_point = (const R*)in->set_point;
+  a.term_w_pp = (const R*)in->lin.terminal_weights;
+  if (in->lin.dyn == nullptr) a.consts = M::template make<double>(in->lin.dyn_shared_host);
+  a.term_tgt[0] = (R)in->set_point_shared;
+  const XV<R, M::NX>* zx_in = a.zx;
+  const R* zu_in = a.zu;
+  if (in->lin.z != nullptr) {
+    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->lin.z,
+                       a.dzx, a.dzu);
+    zx_in = a.dzx;
+    zu_in = a.dzu;
+  }
+  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
+  if (sizeof(R) == 4 && s->wide_qp)
+    hipLaunchKernelGGL((plan_weight_vjp_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, zx_in, zu_in,
+                       (const R*)in->u_prev, n_rows, (const R*)gbar, (R*)g_tw, (R*)g_wu, (R*)g_wdu, (R*)du, ok);
+  else
+    hipLaunchKernelGGL((plan_weight_vjp_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, zx_in, zu_in,
+                       (const R*)in->u_prev, n_rows, (const R*)gbar, (R*)g_tw, (R*)g_wu, (R*)g_wdu, (R*)du, ok);
+}
+
 // debug builds: this unit's copies of the counters (every translation unit has its own __device__ variables)
 static int debug_read_impl(int which, unsigned long long* out) {
 #ifdef CPMPC_FUSED_TIMING
@@ -642,6 +675,6 @@ static int debug_read_impl(int which, unsigned long long* out) {
                              &unpack_z_impl<R, M>,   &dynamics_impl<R, M>,   &rk4_impl<R, M>,      &sim_impl<R, M>,    \
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
-                             &plan_vjp_impl<R, M>};                                                                  \
+                             &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>};                              \
     return &e;                                                                                                       \
   }

@@ -171,6 +171,28 @@ Optimization::PlanGradients Optimization::PlanVjp(const SingleCartPoleParams& dy
   return out;
 }
 
+Optimization::PlanWeightGradients Optimization::PlanWeightVjp(const SingleCartPoleState& current_state,
+                                                              const SingleCartPoleParams& dynamics_params,
+                                                              const double b_x_set_point, const double u_prev,
+                                                              const std::vector<double>& gbar) {
+  if (gbar.empty() || gbar.size() > params_.window_length)
+    throw std::invalid_argument("PlanWeightVjp: gbar must hold between 1 and window_length rows");
+  const auto x0 = current_state.ToVector();
+  const auto dyn = dynamics_params.ToArray();
+  cpmpc_weight_vjp_inputs in{};
+  in.struct_size = sizeof in;
+  in.lin.struct_size = sizeof in.lin;
+  in.lin.dyn_shared_host = dyn.data();
+  in.x0 = x0.data();
+  in.set_point_shared = b_x_set_point;
+  in.u_prev = &u_prev;
+  PlanWeightGradients out{std::vector<double>(4), 0.0, 0.0, std::vector<double>(gbar.size())};
+  const int rc = cpmpc_plan_weight_vjp_batch_host(solver_, 1, &in, static_cast<int>(gbar.size()), gbar.data(),
+                                                  out.g_terminal.data(), &out.g_u, &out.g_du_dt, out.du.data(), nullptr);
+  if (rc != CPMPC_OK) Throw(rc);
+  return out;
+}
+
 void Optimization::StepBatchInto(const double* states_soa, std::size_t B, const SingleCartPoleParams& dynamics_params,
                                  double b_x_set_point, double* u, double* predicted_states, std::int32_t* status,
                                  std::int32_t* iterations, double* final_cost, double* final_equality_l1) {

@@ -167,6 +167,21 @@ class Optimization {
   };
   [[nodiscard]] PlanGradients PlanVjp(const SingleCartPoleParams& dynamics_params, const std::vector<double>& gbar);
 
+  // The gradients of a loss on the last plan's controls with respect to the cost weights: for a cotangent gbar = dL/du+ on
+  // rows 0 .. gbar.size()-1 of u+ = u + du (1 <= gbar.size() <= window_length; later rows are zero) of the undamped,
+  // unclamped Gauss-Newton QP at the previous solution, seen from current_state, b_x_set_point and u_prev (the control before
+  // u_0) -- g_terminal [4] in state order (exactly 0 for an equality row and a zero weight), g_u for u_cost_weight, g_du_dt
+  // for u_derivative_cost_weight -- and that QP's step du [gbar.size()] (include/cpmpc.h: cpmpc_plan_weight_vjp_batch);
+  // throws as PlanSensitivity.
+  struct PlanWeightGradients {
+    std::vector<double> g_terminal;
+    double g_u, g_du_dt;
+    std::vector<double> du;
+  };
+  [[nodiscard]] PlanWeightGradients PlanWeightVjp(const SingleCartPoleState& current_state,
+                                                  const SingleCartPoleParams& dynamics_params, double b_x_set_point,
+                                                  double u_prev, const std::vector<double>& gbar);
+
   const OptimizationParams& params() const noexcept { return params_; }
 
  private:

@@ -165,6 +165,16 @@ PYBIND11_MODULE(pypendulum, m) {
              return py::make_tuple(std::move(r.g_x0), r.g_sp, r.g_up);
            },
            py::arg("dynamics_params"), py::arg("gbar"))
+      // (g_terminal [4], g_u, g_du_dt, du) for a cotangent gbar on the leading rows of the last plan
+      // (Optimization::PlanWeightVjp)
+      .def("plan_weight_vjp",
+           [](Optimization& self, const SingleCartPoleState& current_state, const SingleCartPoleParams& dynamics_params,
+              double b_x_set_point, double u_prev, const std::vector<double>& gbar) {
+             auto r = self.PlanWeightVjp(current_state, dynamics_params, b_x_set_point, u_prev, gbar);
+             return py::make_tuple(std::move(r.g_terminal), r.g_u, r.g_du_dt, std::move(r.du));
+           },
+           py::arg("current_state"), py::arg("dynamics_params"), py::arg("b_x_set_point"), py::arg("u_prev"),
+           py::arg("gbar"))
       // the handle's horizon exceeds cpmpc_max_parity_horizon() (include/cpmpc.h): a per-object status, also in solver_summary()
       .def_property_readonly("horizon_beyond_parity", &Optimization::HorizonBeyondParity);
 

@@ -549,7 +549,8 @@ int cpmpc_plan_sensitivity_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_ga
  * linearisation, one pass over Phi and Gamma, one terminal solve, whatever n_rows is.
  * What the gradients are: those of the UNDAMPED, UNCLAMPED Gauss-Newton QP at the linearisation point z, exactly the
  * transposes of what cpmpc_plan_sensitivity_batch returns.  What they are NOT: derivatives of the converged NLP solution,
- * of a clamped control, or with respect to the dynamics parameters, the weights or z.  They do not depend on x0, the
+ * of a clamped control, or with respect to the dynamics parameters, the weights (cpmpc_plan_weight_vjp_batch has those) or
+ * z.  They do not depend on x0, the
  * set-point's value, u_prev's value, the residuals or the defects.
  *
  * gbar [n_rows][B], g_x0 [NX][B], g_sp [B], g_up [B] in the handle's dtype, batch fastest; each output is nullable and
@@ -570,6 +571,50 @@ int cpmpc_plan_vjp_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_gain_input
                               const double* gbar_host /* [n_rows][B] */, double* g_x0_host /* nullable */,
                               double* g_sp_host /* nullable */, double* g_up_host /* nullable */,
                               int32_t* ok_host /* nullable */);
+/* ---- weight gradients: a cotangent on the planned controls pulled back to the cost weights ---- */
+/* For a caller who tunes the controller itself: given gbar = dL/du+ [n_rows] per problem on the controls u+ = u + du that
+ * the QP at z plans (rows at and beyond n_rows are zero), the gradients of L with respect to the cost weights
+ *     g_tw [NX] per problem   the terminal weights in state order: -2 w_t yx_t (x_{S-1,t} + dx_{S-1,t} - target_t) for a cost
+ *                             row with w_t > 0; exactly 0 for an equality row (w_t < 0) and for w_t = 0,
+ *     g_wu      scalar        u_cost_weight:             -2 w_u  sum_k y_k (u_k + du_k),
+ *     g_wdu     scalar        u_derivative_cost_weight:  -2 w_du [y_0 (u_0 + du_0 - u_prev)
+ *                                                                 + sum_{k<N-1} (y_k - y_{k+1}) (u_k + du_k - u_{k+1} - du_{k+1})],
+ * and, on request, du [n_rows] itself: the primal step of that QP (one undamped SQP step without a line search).  dz is the
+ * QP's solution and y the solution of the same KKT system with gbar in the control rows; both are solved in condensed
+ * form in one kernel over Phi and Gamma with one LDL^T.  w_u and w_du are the handle's weights,
+ * clamped at 0 as in a step.
+ * What the gradients are: those of the UNDAMPED, UNCLAMPED Gauss-Newton QP linearised at z.  At a converged z (dz -> 0) they
+ * are the implicit-function derivative of the Gauss-Newton stationarity condition.  What they are NOT: derivatives through
+ * the line search, the +-u_limit / +-b_x_limit retraction or the earlier iterations of the SQP, and there are none with
+ * respect to the dynamics parameters.  Unlike K, k_sp and k_up they DO depend on x0, the set-point and u_prev, which is why
+ * this call takes them.
+ *
+ * gbar [n_rows][B], g_tw [NX][B], g_wu [B], g_wdu [B], du [n_rows][B] in the handle's dtype, batch fastest; every output is
+ * nullable and only those given are computed; at least one must be given; gbar may be NULL only when du is the only
+ * output; 1 <= n_rows <= N.  ok, the preconditions on `lin` and the error codes are those of cpmpc_plan_vjp_batch; a problem
+ * with ok = 0 gets NaN in every output.  Float handles carry eta, a, S, the LDL^T, both solves and the sums in double; with
+ * cpmpc_wide_qp() Psi and w_k as well.  Every output is bitwise the same whichever others are asked for with it, and
+ * n_rows < N gives bitwise what n_rows = N gives for gbar padded with zeros.  Asynchronous on `stream`; the call writes only
+ * scratch that every step recomputes before it reads it (the linearisation's Phi, Gamma and defects, the rows of W and T; a z
+ * given in `lin` goes through the step buffers): a step's results do not depend on calls made in between. */
+typedef struct cpmpc_weight_vjp_inputs {
+  uint64_t struct_size;     /* = sizeof(cpmpc_weight_vjp_inputs) */
+  cpmpc_gain_inputs lin;    /* dyn, terminal_weights, z: as cpmpc_plan_vjp_batch (lin.struct_size = sizeof(cpmpc_gain_inputs)) */
+  const void* x0;           /* [NX][B] the states the plan starts from, required */
+  double set_point_shared;  /* the b_x set-point of every problem, used when set_point is NULL */
+  const void* set_point;    /* [B] per-problem set-points, or NULL: as cpmpc_step_inputs */
+  const void* u_prev;       /* [B] the control before u_0 (the row w_du (u_0 - u_prev)), or NULL: 0 for every problem */
+} cpmpc_weight_vjp_inputs;
+int cpmpc_plan_weight_vjp_batch(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows,
+                                const void* gbar /* [n_rows][B] */, void* g_tw /* [NX][B], nullable */,
+                                void* g_wu /* [B], nullable */, void* g_wdu /* [B], nullable */,
+                                void* du /* [n_rows][B], nullable */, int32_t* ok /* nullable */, void* stream);
+/* The same with HOST doubles (every pointer of `in`, gbar_host and the outputs); synchronous.  Used by the C++ facade
+ * (pendulum::Optimization::PlanWeightVjp). */
+int cpmpc_plan_weight_vjp_batch_host(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows,
+                                     const double* gbar_host /* [n_rows][B] */, double* g_tw_host /* nullable */,
+                                     double* g_wu_host /* nullable */, double* g_wdu_host /* nullable */,
+                                     double* du_host /* nullable */, int32_t* ok_host /* nullable */);
 /* The first-order re-plan of the whole horizon, one elementwise pass over rows k < n_rows:
  *     u_out[k] = clamp(u_nom[k] + K[k] . wrap(x - x_nom) + k_sp[k] (sp - sp_nom) + k_up[k] (u_prev - u_prev_nom), +-u_limit).
  * A step re-rolls every state of its initial guess from x0 and the controls, so the updated controls are a complete warm
