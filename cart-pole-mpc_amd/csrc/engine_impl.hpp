@@ -511,31 +511,56 @@ static void sim_impl(int64_t B, const double* dyn_shared_host, const double* fex
                      ext_from_host<R>(fext_host), (const R*)fext, n_sub, (R)h_last, (const R*)u, (R*)state);
 }
 
-// ---- feedback gains ------------------------------------------------------------------------------------------------
-// Linearise at z exactly as linearize_batch_impl does (a caller's z goes through the step buffers dzx / dzu, which hold no
-// state between calls; z == NULL: the warm start itself, read only), then one lane per problem over Phi and Gamma.  The
-// call writes Phi, Gamma, cs, Wk and Tk: scratch that every step recomputes before it reads it.
+// ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
+// All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
+// linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
+// z == NULL: the warm start itself, read only), then one lane per problem over Phi and Gamma.  Each call writes Phi,
+// Gamma and cs, and the rows of Wk and Tk its kernel stores: scratch that every step recomputes before it reads it.
 template <typename R, typename M>
-static void feedback_gain_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, int32_t* ok,
-                               hipStream_t st) {
+static SolverArgs<R, M> gain_args(const cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in) {
   SolverArgs<R, M> a;
   fill_args<R, M>(s, B, a);
   a.dyn = (const R*)in->dyn;
   a.term_w_pp = (const R*)in->terminal_weights;
   if (in->dyn == nullptr) a.consts = M::template make<double>(in->dyn_shared_host);
-  const XV<R, M::NX>* zx_in = a.zx;
-  const R* zu_in = a.zu;
-  if (in->z != nullptr) {
-    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->z,
+  return a;
+}
+
+// the linearisation point of a call, as its kernel reads it
+template <typename R, typename M>
+struct PlanPoint {
+  const XV<R, M::NX>* zx;
+  const R* zu;
+};
+
+template <typename R, typename M>
+static PlanPoint<R, M> linearize_at(const cpmpc_solver* s, const SolverArgs<R, M>& a, const void* z, hipStream_t st) {
+  PlanPoint<R, M> at = {a.zx, a.zu};
+  if (z != nullptr) {
+    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(a.B), dim3(64), 0, st, a.B, s->cap, s->S, s->N, (const R*)z,
                        a.dzx, a.dzu);
-    zx_in = a.dzx;
-    zu_in = a.dzu;
+    at = {a.dzx, a.dzu};
   }
-  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
-  if (sizeof(R) == 4 && s->wide_qp)
-    hipLaunchKernelGGL((feedback_gain_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, ok);
-  else
-    hipLaunchKernelGGL((feedback_gain_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, ok);
+  launch_linearize<R, M>(a, s->SP, at.zx, at.zu, nullptr, st);
+  return at;
+}
+
+// KERNEL<R, M, WIDEQ> of the enclosing template's R and M, one lane per problem: the wide form for a float handle s with
+// cpmpc_wide_qp(), else the plain one.  Undefined again below plan_weight_vjp_impl, its last user.
+#define CPMPC_LAUNCH_WIDE_OR_PLAIN(KERNEL, s, B, st, ...)                                                \
+  do {                                                                                                   \
+    if (sizeof(R) == 4 && (s)->wide_qp)                                                                  \
+      hipLaunchKernelGGL((KERNEL<R, M, true>), grid_for(B), dim3(64), 0, st, __VA_ARGS__);               \
+    else                                                                                                 \
+      hipLaunchKernelGGL((KERNEL<R, M, false>), grid_for(B), dim3(64), 0, st, __VA_ARGS__);              \
+  } while (0)
+
+template <typename R, typename M>
+static void feedback_gain_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, int32_t* ok,
+                               hipStream_t st) {
+  const SolverArgs<R, M> a = gain_args<R, M>(s, B, in);
+  linearize_at<R, M>(s, a, in->z, st);
+  CPMPC_LAUNCH_WIDE_OR_PLAIN(feedback_gain_kernel, s, B, st, a, n_rows, (R*)K, ok);
 }
 
 template <typename R, typename M>
@@ -545,32 +570,13 @@ static void feedback_apply_impl(int64_t B, const void* u_nom, const void* K0, co
                      (const R*)u_nom, (const R*)K0, (const R*)x_nom, (const R*)x, (R)u_limit, (R*)u_out);
 }
 
-// ---- plan sensitivities ----------------------------------------------------------------------------------------------
-// feedback_gain_impl's linearisation at z, then plan_sensitivity_kernel for the outputs that are not null; the same
-// scratch is written.
+// plan_sensitivity_kernel for the outputs that are not null
 template <typename R, typename M>
 static void plan_sensitivity_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, void* K, void* k_sp,
                                   void* k_up, int32_t* ok, hipStream_t st) {
-  SolverArgs<R, M> a;
-  fill_args<R, M>(s, B, a);
-  a.dyn = (const R*)in->dyn;
-  a.term_w_pp = (const R*)in->terminal_weights;
-  if (in->dyn == nullptr) a.consts = M::template make<double>(in->dyn_shared_host);
-  const XV<R, M::NX>* zx_in = a.zx;
-  const R* zu_in = a.zu;
-  if (in->z != nullptr) {
-    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->z,
-                       a.dzx, a.dzu);
-    zx_in = a.dzx;
-    zu_in = a.dzu;
-  }
-  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
-  if (sizeof(R) == 4 && s->wide_qp)
-    hipLaunchKernelGGL((plan_sensitivity_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, (R*)k_sp,
-                       (R*)k_up, ok);
-  else
-    hipLaunchKernelGGL((plan_sensitivity_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, n_rows, (R*)K, (R*)k_sp,
-                       (R*)k_up, ok);
+  const SolverArgs<R, M> a = gain_args<R, M>(s, B, in);
+  linearize_at<R, M>(s, a, in->z, st);
+  CPMPC_LAUNCH_WIDE_OR_PLAIN(plan_sensitivity_kernel, s, B, st, a, n_rows, (R*)K, (R*)k_sp, (R*)k_up, ok);
 }
 
 template <typename R, typename M>
@@ -581,65 +587,29 @@ static void plan_update_impl(int64_t B, int n_rows, const cpmpc_plan_update* u, 
                      (const R*)u->u_prev, (R)u->u_limit, (R*)u->u_out);
 }
 
-// ---- reverse-mode plan sensitivities ---------------------------------------------------------------------------------
-// plan_sensitivity_impl's linearisation at z, then plan_vjp_kernel for the outputs that are not null.  Only the
-// linearisation scratch (Phi, Gamma, cs) is written: the kernel itself writes no workspace array.
+// reverse mode: plan_vjp_kernel for the outputs that are not null.  The kernel itself writes no workspace array.
 template <typename R, typename M>
 static void plan_vjp_impl(cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in, int n_rows, const void* gbar, void* g_x0,
                           void* g_sp, void* g_up, int32_t* ok, hipStream_t st) {
-  SolverArgs<R, M> a;
-  fill_args<R, M>(s, B, a);
-  a.dyn = (const R*)in->dyn;
-  a.term_w_pp = (const R*)in->terminal_weights;
-  if (in->dyn == nullptr) a.consts = M::template make<double>(in->dyn_shared_host);
-  const XV<R, M::NX>* zx_in = a.zx;
-  const R* zu_in = a.zu;
-  if (in->z != nullptr) {
-    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->z,
-                       a.dzx, a.dzu);
-    zx_in = a.dzx;
-    zu_in = a.dzu;
-  }
-  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
-  if (sizeof(R) == 4 && s->wide_qp)
-    hipLaunchKernelGGL((plan_vjp_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, n_rows, (const R*)gbar, (R*)g_x0,
-                       (R*)g_sp, (R*)g_up, ok);
-  else
-    hipLaunchKernelGGL((plan_vjp_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, n_rows, (const R*)gbar, (R*)g_x0,
-                       (R*)g_sp, (R*)g_up, ok);
+  const SolverArgs<R, M> a = gain_args<R, M>(s, B, in);
+  linearize_at<R, M>(s, a, in->z, st);
+  CPMPC_LAUNCH_WIDE_OR_PLAIN(plan_vjp_kernel, s, B, st, a, n_rows, (const R*)gbar, (R*)g_x0, (R*)g_sp, (R*)g_up, ok);
 }
 
-// ---- weight gradients of the plan ------------------------------------------------------------------------------------
-// plan_vjp_impl's linearisation at z, then plan_weight_vjp_kernel for the outputs that are not null, with the inputs the
-// primal solve needs (x0, the set-point, u_prev) where a step has them.  The linearisation scratch (Phi, Gamma, cs) and the
-// rows of W and T are written, nothing else.
+// weight gradients: plan_weight_vjp_kernel for the outputs that are not null, with the inputs the primal solve needs
+// (x0, the set-point, u_prev) where a step has them
 template <typename R, typename M>
 static void plan_weight_vjp_impl(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows, const void* gbar,
                                  void* g_tw, void* g_wu, void* g_wdu, void* du, int32_t* ok, hipStream_t st) {
-  SolverArgs<R, M> a;
-  fill_args<R, M>(s, B, a);
+  SolverArgs<R, M> a = gain_args<R, M>(s, B, &in->lin);
   a.x0 = (const R*)in->x0;
-  a.dyn = (const R*)in->lin.dyn;
   a.set_point = (const R*)in->set_point;
-  a.term_w_pp = (const R*)in->lin.terminal_weights;
-  if (in->lin.dyn == nullptr) a.consts = M::template make<double>(in->lin.dyn_shared_host);
   a.term_tgt[0] = (R)in->set_point_shared;
-  const XV<R, M::NX>* zx_in = a.zx;
-  const R* zu_in = a.zu;
-  if (in->lin.z != nullptr) {
-    hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)in->lin.z,
-                       a.dzx, a.dzu);
-    zx_in = a.dzx;
-    zu_in = a.dzu;
-  }
-  launch_linearize<R, M>(a, s->SP, zx_in, zu_in, nullptr, st);
-  if (sizeof(R) == 4 && s->wide_qp)
-    hipLaunchKernelGGL((plan_weight_vjp_kernel<R, M, true>), grid_for(B), dim3(64), 0, st, a, zx_in, zu_in,
-                       (const R*)in->u_prev, n_rows, (const R*)gbar, (R*)g_tw, (R*)g_wu, (R*)g_wdu, (R*)du, ok);
-  else
-    hipLaunchKernelGGL((plan_weight_vjp_kernel<R, M, false>), grid_for(B), dim3(64), 0, st, a, zx_in, zu_in,
-                       (const R*)in->u_prev, n_rows, (const R*)gbar, (R*)g_tw, (R*)g_wu, (R*)g_wdu, (R*)du, ok);
+  const PlanPoint<R, M> at = linearize_at<R, M>(s, a, in->lin.z, st);
+  CPMPC_LAUNCH_WIDE_OR_PLAIN(plan_weight_vjp_kernel, s, B, st, a, at.zx, at.zu, (const R*)in->u_prev, n_rows, (const R*)gbar,
+                             (R*)g_tw, (R*)g_wu, (R*)g_wdu, (R*)du, ok);
 }
+#undef CPMPC_LAUNCH_WIDE_OR_PLAIN
 
 // debug builds: this unit's copies of the counters (every translation unit has its own __device__ variables)
 static int debug_read_impl(int which, unsigned long long* out) {

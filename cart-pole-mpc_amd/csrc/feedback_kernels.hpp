@@ -21,18 +21,37 @@
 // never read back in float -- a pass of its own (k descending, NX right-hand sides at once) forms
 //     w_k . Q = psi_s Gamma_k - upsilon_k (w_{k+1} . Q),   psi_s = Phi_{s+1}^T psi_{s+1},   psi_{S-2} = diag(w) Q
 // in double and leaves the rows the caller asked for in the slots of W.
-// The pivot step of sweep 1, the LDL^T with its solves and the adjoint product psi <- Phi_s^T psi are the blocks of
-// condensed_qp.hpp that qp_ls_kernel is made of too.  The rest of sweep 1 below still restates "sweep 1 (k descending)" of
-// qp_ls_kernel (without the gradient g, gw, rho, the residuals and the free response): tried one at a time in that kernel,
-// the rank-one update of S as a shared function cost its float instantiations a wave per SIMD (4 states 166 -> 170 VGPRs,
-// 3 -> 2 waves; 6 states 256 -> 256 + 96 AGPRs, 2 -> 1) and Psi <- Psi Phi_s the 6-state one (256 -> 256 + 14, 2 -> 1), with
-// no arithmetic opcode changed; they stay in place in both kernels, and a fix there is to be carried over here.
+// What is shared (condensed_qp.hpp): with qp_ls_kernel the pivot step of sweep 1, the LDL^T with its solves and the adjoint
+// product psi <- Phi_s^T psi; with the three other sensitivity kernels (plan_sensitivity_kernels.hpp, plan_vjp_kernels.hpp,
+// plan_weight_vjp_kernels.hpp) also the set-up of S, Psi and w, Psi <- Psi Phi_s and the column step of pass 1b (which
+// plan_sensitivity_kernel restates: it runs slower with the function); gain_row below is the gain rows of the ascending
+// pass, plan_sensitivity_kernel's too.  What is not: the loop over the controls
+// (Gamma's software pipeline, the w_k row, the stores), which differs from kernel to kernel in what it carries, and the
+// rank-one update of S, which costs the 6-state instantiations a wave as a function (the figures are in condensed_qp.hpp).
 // A lane whose d_k or LDL^T pivot is not positive (or not a number: a poisoned parameter set) reports ok = 0 and gets
 // NaN rows; nothing of a lane depends on its neighbours.
 #pragma once
 #include "mpc_kernels.hpp"
 
 namespace cpmpc {
+
+// Row k of the gains from row k-1 (ascending pass): k_row_k = - (w_k . Q) / d_k - upsilon_{k-1} k_row_{k-1}, NaN for a lane that
+// is not ok.  wr is w_k from the slots of W -- in the wide QP w_k . Q itself, which pass 1b left there.  Shared with
+// plan_sensitivity_kernel.
+template <bool kWideQP, typename R, typename W, int NX>
+__device__ __forceinline__ void gain_row(const R (&wr)[NX], const W (&Qm)[NX][NX], const W inv_d, const W ups_prev,
+                                         W (&kprev)[NX], const bool pd_ok, R* __restrict__ K_out, const int kk, const int64_t B,
+                                         const unsigned p) {
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    W wq;
+    if constexpr (kWideQP) wq = (W)wr[j];
+    else wq = dot<W>(wr, Qm[j]);
+    const W kr = -(wq * inv_d) - ups_prev * kprev[j];
+    kprev[j] = kr;
+    K_out[((int64_t)kk * NX + j) * B + p] = pd_ok ? (R)kr : R(__builtin_nan(""));
+  }
+}
 
 template <typename R, typename M, bool WIDEQ>
 __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M> a, const int n_rows, R* __restrict__ K_out,
@@ -55,20 +74,11 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
 
   // ---- sweep 1 (k descending), lambda = 0 ---------------------------------------------------------
   W Sm[NX][NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-#pragma unroll
-    for (int j = 0; j < NX; ++j) Sm[i][j] = WO::of(R(0));
-  bool pd_ok = true;
   Q Psi[NX][NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r)
-#pragma unroll
-    for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
+  Q wk[NX];  // w_{k+1}, then w_k
+  sweep1_init(Rw, Sm, Psi, wk);
+  bool pd_ok = true;
   {
-    Q wk[NX];  // w_{k+1}, then w_k
-#pragma unroll
-    for (int r = 0; r < NX; ++r) wk[r] = Q(0);
     R d_next = R(1);
     const XVn* __restrict__ gam_p = a.Gam + p;
     XVn G_nx = gam_p[(int64_t)(N - 1) * st];  // software pipeline: column k-1 is loaded before column k is consumed
@@ -102,25 +112,7 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
           for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
         }
       }
-      // Psi <- Psi Phi_s
-      Q T[NX][NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) T[r][c] = Q(0);
-#pragma unroll
-      for (int m = 0; m < NX; ++m) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + m) * st + p], row);
-#pragma unroll
-        for (int r = 0; r < NX; ++r)
-#pragma unroll
-          for (int c = 0; c < NX; ++c) T[r][c] += Psi[r][m] * Q(row[c]);
-      }
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+      psi_times_phi(Psi, a.Phi, s, st, p);
     }
   }
 
@@ -156,15 +148,10 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
         R gk[NX];
         unpack<R, NX>(a.Gam[(int64_t)kk * st + p], gk);
         const V4 T = a.Tk[(int64_t)kk * st + p];
+        pass1b_step(psi, gk, (W)T.y, om);
         R wq[NX];
 #pragma unroll
-        for (int j = 0; j < NX; ++j) {
-          W pg = psi[0][j] * (W)gk[0];
-#pragma unroll
-          for (int m = 1; m < NX; ++m) pg += psi[m][j] * (W)gk[m];
-          om[j] = pg - (W)T.y * om[j];
-          wq[j] = (R)om[j];
-        }
+        for (int j = 0; j < NX; ++j) wq[j] = (R)om[j];
         if (kk < n_rows) a.Wk[(int64_t)kk * st + p] = pack<R, NX>(wq);
       }
       if (s == 0) break;
@@ -174,7 +161,6 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
 
   // ---- ascending pass: U^T K = - D^-1 W Q, the first n_rows rows -------------------------------------
   if (ok_out != nullptr) ok_out[p] = pd_ok ? 1 : 0;
-  const R qnan = R(__builtin_nan(""));
   W kprev[NX];
 #pragma unroll
   for (int j = 0; j < NX; ++j) kprev[j] = W(0);
@@ -183,15 +169,7 @@ __global__ __launch_bounds__(64) void feedback_gain_kernel(const SolverArgs<R, M
     R wr[NX];
     unpack<R, NX>(a.Wk[(int64_t)kk * st + p], wr);
     const V4 T = a.Tk[(int64_t)kk * st + p];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      W wq;
-      if constexpr (kWideQP) wq = (W)wr[j];
-      else wq = dot<W>(wr, Qm[j]);
-      const W kr = -(wq * (W)T.z) - ups_prev * kprev[j];
-      kprev[j] = kr;
-      K_out[((int64_t)kk * NX + j) * a.B + p] = pd_ok ? (R)kr : qnan;
-    }
+    gain_row<kWideQP>(wr, Qm, (W)T.z, ups_prev, kprev, pd_ok, K_out, kk, a.B, p);
     ups_prev = (W)T.y;
   }
 }

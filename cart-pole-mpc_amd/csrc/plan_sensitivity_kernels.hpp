@@ -22,14 +22,16 @@
 // WIDEQ (float handles with cpmpc_wide_qp()): as in feedback_gain_kernel the descending pass "1b" forms w_k . v in double
 // for the NX gain columns and leaves them in the slots of W; the two further scalars per control, w_k . q_sp and w_k . dq,
 // go to the .x and .w lanes of the Tk element, which that kernel leaves unused: no new workspace.
-// Sweep 1, the solves of the gain columns, pass 1b and the gain rows of the ascending pass restate feedback_gain_kernel
-// expression by expression (as that kernel restates qp_ls_kernel, and for the same reason: sharing the source would move
-// the register allocation of the existing instantiations), so K asked for here is the K of that kernel; a fix there is
-// to be carried over here.
+// The pieces of sweep 1 are condensed_qp.hpp's, the gain rows of the ascending pass are gain_row of feedback_kernels.hpp:
+// the code feedback_gain_kernel runs, so K asked for here is the K of that kernel.  The loop over the controls and the
+// rank-one update of S are this kernel's own text (condensed_qp.hpp says why), and so is the column step of pass 1b, which
+// restates pass1b_step of condensed_qp.hpp: with that function the two wide float forms compile smaller (4-state 148 -> 128
+// VGPRs, 6-state 256 + 22 AGPRs -> 246) and the 6-state one runs 4 - 6 % slower on an MI355X (65 536 problems, all outputs,
+// n_rows = N: 0.223 -> 0.236 ms; the 4-state one 2 - 5 % faster).  A fix to pass1b_step is to be carried over here.
 // A lane whose d_k or LDL^T pivot is not positive (or not a number) reports ok = 0 and gets NaN in every output; nothing
 // of a lane depends on its neighbours.
 #pragma once
-#include "mpc_kernels.hpp"
+#include "feedback_kernels.hpp"
 
 namespace cpmpc {
 
@@ -56,19 +58,10 @@ __global__ __launch_bounds__(64) void plan_sensitivity_kernel(const SolverArgs<R
 
   // ---- sweep 1 (k descending), lambda = 0 ---------------------------------------------------------
   W Sm[NX][NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-#pragma unroll
-    for (int j = 0; j < NX; ++j) Sm[i][j] = WO::of(R(0));
-  bool pd_ok = true;
   Q Psi[NX][NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r)
-#pragma unroll
-    for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
   Q wk[NX];  // w_{k+1}, then w_k; w_0 when the sweep ends
-#pragma unroll
-  for (int r = 0; r < NX; ++r) wk[r] = Q(0);
+  sweep1_init(Rw, Sm, Psi, wk);
+  bool pd_ok = true;
   R inv_d0 = R(0);  // 1 / d_0 when the sweep ends
   {
     R d_next = R(1);
@@ -105,25 +98,7 @@ __global__ __launch_bounds__(64) void plan_sensitivity_kernel(const SolverArgs<R
           for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
         }
       }
-      // Psi <- Psi Phi_s
-      Q T[NX][NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) T[r][c] = Q(0);
-#pragma unroll
-      for (int m = 0; m < NX; ++m) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + m) * st + p], row);
-#pragma unroll
-        for (int r = 0; r < NX; ++r)
-#pragma unroll
-          for (int c = 0; c < NX; ++c) T[r][c] += Psi[r][m] * Q(row[c]);
-      }
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+      psi_times_phi(Psi, a.Phi, s, st, p);
     }
   }
 
@@ -234,17 +209,7 @@ __global__ __launch_bounds__(64) void plan_sensitivity_kernel(const SolverArgs<R
     R wr[NX];
     const V4 T = a.Tk[(int64_t)kk * st + p];
     if (!kWideQP || want_K) unpack<R, NX>(a.Wk[(int64_t)kk * st + p], wr);
-    if (want_K) {
-#pragma unroll
-      for (int j = 0; j < NX; ++j) {
-        W wq;
-        if constexpr (kWideQP) wq = (W)wr[j];
-        else wq = dot<W>(wr, Qm[j]);
-        const W kr = -(wq * (W)T.z) - ups_prev * kprev[j];
-        kprev[j] = kr;
-        K_out[((int64_t)kk * NX + j) * a.B + p] = pd_ok ? (R)kr : qnan;
-      }
-    }
+    if (want_K) gain_row<kWideQP>(wr, Qm, (W)T.z, ups_prev, kprev, pd_ok, K_out, kk, a.B, p);
     if (want_sp) {
       W wq;
       if constexpr (kWideQP) wq = (W)T.x;

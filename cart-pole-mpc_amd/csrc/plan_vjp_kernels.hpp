@@ -25,10 +25,9 @@
 // not null (a wave-uniform choice: the pointers are kernel arguments).  eta, a, q and the three products are carried in
 // the wide type of wide.hpp; with WIDEQ on a float handle Psi and w_k are double in sweep 1 already, so the wide form
 // needs no second pass.
-// Sweep 1 restates that of plan_sensitivity_kernel expression by expression (the Gamma software pipeline, tridiag_pivot,
-// Psi <- Psi Phi_s, S accumulated in W, the TerminalLDL of condensed_qp.hpp) instead of sharing its source, as that kernel
-// restates feedback_gain_kernel and for the same reason: the register allocation of the existing instantiations must
-// not move.  A fix there is to be carried over here.
+// Sweep 1 is made of the pieces of condensed_qp.hpp that plan_sensitivity_kernel uses (the set-up of S, Psi and w,
+// tridiag_pivot, Psi <- Psi Phi_s, the TerminalLDL); the loop over the controls, which here prefetches gbar's row beside
+// Gamma's column, and the rank-one update of S are this kernel's own text (condensed_qp.hpp says why).
 // A lane whose d_k or LDL^T pivot is not positive (or not a number) reports ok = 0 and gets NaN in every output; nothing
 // of a lane depends on its neighbours.
 #pragma once
@@ -58,19 +57,10 @@ __global__ __launch_bounds__(64) void plan_vjp_kernel(const SolverArgs<R, M> a, 
 
   // ---- sweep 1 (k descending), lambda = 0, with the adjoint recurrence ---------------------------------
   W Sm[NX][NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i)
-#pragma unroll
-    for (int j = 0; j < NX; ++j) Sm[i][j] = WO::of(R(0));
-  bool pd_ok = true;
   Q Psi[NX][NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r)
-#pragma unroll
-    for (int c = 0; c < NX; ++c) Psi[r][c] = (r == c) ? Q(Rw[r]) : Q(0);
   Q wk[NX];  // w_{k+1}, then w_k; w_0 when the sweep ends
-#pragma unroll
-  for (int r = 0; r < NX; ++r) wk[r] = Q(0);
+  sweep1_init(Rw, Sm, Psi, wk);
+  bool pd_ok = true;
   R inv_d0 = R(0);  // 1 / d_0 when the sweep ends
   W eta = W(0);     // eta_{k+1}, then eta_k; eta_0 when the sweep ends
   W av[NX];         // a = sum_k w_k eta_k / d_k
@@ -113,25 +103,7 @@ __global__ __launch_bounds__(64) void plan_vjp_kernel(const SolverArgs<R, M> a, 
           for (int j2 = 0; j2 <= i2; ++j2) Sm[i2][j2] += wi * (W)wk[j2];
         }
       }
-      // Psi <- Psi Phi_s
-      Q T[NX][NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) T[r][c] = Q(0);
-#pragma unroll
-      for (int m = 0; m < NX; ++m) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + m) * st + p], row);
-#pragma unroll
-        for (int r = 0; r < NX; ++r)
-#pragma unroll
-          for (int c = 0; c < NX; ++c) T[r][c] += Psi[r][m] * Q(row[c]);
-      }
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+      psi_times_phi(Psi, a.Phi, s, st, p);
     }
   }
 

@@ -41,9 +41,11 @@
 // In float handles eta, a, S, rho, the free response, the LDL^T, both solves and the ascending pass are carried in the wide
 // type of wide.hpp.  One kernel in all eight instantiations: the double 6-state form holds both solves without scratch
 // (DESIGN.md section 5d has the resource lines), so the two-kernel split was not needed.
-// Sweep 1 restates qp_ls_kernel's and plan_vjp_kernel's expression by expression instead of sharing their source, for the
-// reason those give: the register allocation of the existing instantiations must not move.  A fix there is to be carried
-// over here.
+// Sweep 1 uses the pieces of condensed_qp.hpp that plan_vjp_kernel uses, except sweep1_init: the set-up of S, Psi and w
+// stays written out here (the note at that set-up says why).  Pass 1b uses the column step that plan_sensitivity_kernel
+// uses for its two scalars.  The primal quantities beside them restate qp_ls_kernel's sweep 1 (that kernel shares none of
+// it: its figures are in condensed_qp.hpp), and the loop over the controls and the rank-one update of S, here in one loop
+// with rho and a, are this kernel's own text.
 // A lane whose d_k or LDL^T pivot is not positive (or not a number) reports ok = 0 and gets NaN in every output; nothing
 // of a lane depends on its neighbours.
 #pragma once
@@ -96,6 +98,8 @@ __global__ __launch_bounds__(64) void plan_weight_vjp_kernel(const SolverArgs<R,
   }
 
   // ---- sweep 1 (k descending), lambda = 0, primal and adjoint recurrences side by side -------------------------------
+  // (not sweep1_init: with it AND psi_times_phi the double 4-state form keeps Psi as one vector value, the multiply-adds
+  // pair up differently and g_wu, g_wdu, g_tw and du move by up to 4e-11, 6e-11, 4e-15 and 4e-12 -- measured on an MI355X)
   W Sm[NX][NX], rho[NX];
 #pragma unroll
   for (int i = 0; i < NX; ++i) {
@@ -187,25 +191,7 @@ __global__ __launch_bounds__(64) void plan_weight_vjp_kernel(const SolverArgs<R,
 #pragma unroll
         for (int r = 0; r < NX; ++r) ha[r] += dot<W>(Psi[r], c);
       }
-      // Psi <- Psi Phi_s
-      Q T[NX][NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) T[r][c] = Q(0);
-#pragma unroll
-      for (int m = 0; m < NX; ++m) {
-        R row[NX];
-        unpack<R, NX>(a.Phi[(int64_t)(NX * s + m) * st + p], row);
-#pragma unroll
-        for (int r = 0; r < NX; ++r)
-#pragma unroll
-          for (int c = 0; c < NX; ++c) T[r][c] += Psi[r][m] * Q(row[c]);
-      }
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) Psi[r][c] = T[r][c];
+      psi_times_phi(Psi, a.Phi, s, st, p);
     }
     // Psi is now diag(w) Phi_{S-2} ... Phi_0: the contribution of dx_0 = -c_init
 #pragma unroll
@@ -255,13 +241,7 @@ __global__ __launch_bounds__(64) void plan_weight_vjp_kernel(const SolverArgs<R,
         R gk[NX];
         unpack<R, NX>(a.Gam[(int64_t)kk * st + p], gk);
         V4 T = a.Tk[(int64_t)kk * st + p];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          W pg = psx[0][j] * (W)gk[0];
-#pragma unroll
-          for (int m = 1; m < NX; ++m) pg += psx[m][j] * (W)gk[m];
-          omx[j] = pg - (W)T.y * omx[j];
-        }
+        pass1b_step(psx, gk, (W)T.y, omx);
         if (kk < n_asc) {
           T.x = (R)(-((W)T.x + omx[0]));
           T.w = (R)((W)T.w - omx[1]);
