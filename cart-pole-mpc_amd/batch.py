@@ -739,6 +739,115 @@ def plan_update(u_nom, K=None, x_nom=None, x=None, k_sp=None, sp_nom=None, sp=No
     return out
 
 
+def _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, names):
+    """One cpmpc_sim_step_jac_batch call on the current stream for the outputs in `names` (fields of cpmpc_sim_jac)."""
+    m, nx, npar = _model_dims(model)
+    dtp = state.dtype
+    _require_cuda_tensor(state, "state", dtp)
+    if state.dim() != 2 or state.shape[0] != nx:
+        raise ValueError("state must be [%d, B]" % nx)
+    B = int(state.shape[1])
+    _require_cuda_tensor(u, "u", dtp, (B,))
+    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)   # read by the call itself, before it returns
+    a = capi.SimJac(struct_size=C.sizeof(capi.SimJac))
+    a.state, a.u = state.data_ptr(), u.data_ptr()
+    a.fext_host = C.cast(shared, C.POINTER(C.c_double))
+    if fext is not None:
+        _require_cuda_tensor(fext, "fext", dtp, (4, B))
+        a.fext = fext.data_ptr()
+    if gbar is not None:
+        _require_cuda_tensor(gbar, "gbar", dtp, (nx, B))
+        a.gbar = gbar.data_ptr()
+    shapes = {"x_new": (nx, B), "A": (nx, nx, B), "Bu": (nx, B), "gx": (nx, B), "gu": (B,)}
+    res = {}
+    for name in names:
+        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
+        setattr(a, name, res[name].data_ptr())
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_step_jac_batch(m, _CAPI_DTYPE[dtp], B, capi.dbl_array(params, npar), float(dt),
+                                                        C.byref(a), _stream_ptr()))
+    return res
+
+
+def sim_step_jacobian(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+                      want=("x_new", "A", "Bu")):
+    """BatchSimulator.step's map x+ = plant(x, u) with its first derivatives (include/cpmpc.h: cpmpc_sim_step_jac_batch):
+    for state [nx, B] (read, not changed) and u [B] a dict with the entries named in `want`,
+        "x_new" [nx, B]      the state after dt (the simulator's sub-steps: 1 ms, a shorter last one, angles wrapped),
+        "A"     [nx, nx, B]  dx+/dx,
+        "Bu"    [nx, B]      dx+/du, the control held over the step,
+    the product of the sub-steps' RK4 Jacobians.  params, dt, f_base / f_mass / fext as BatchSimulator.step's.  Not
+    differentiated: the dynamics parameters, the external forces and dt.  Only what is named is computed."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("x_new", "A", "Bu") for w in want):
+        raise ValueError("want must name at least one of 'x_new', 'A', 'Bu'")
+    return _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, None, want)
+
+
+def sim_step_vjp(params, dt, state, u, gbar, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+                 want=("x", "u")):
+    """The reverse mode of sim_step_jacobian: a cotangent gbar = dL/dx+ [nx, B] on the state after the step pulled back to
+    the inputs named in `want` -- a dict with
+        "x" [nx, B]  A^T gbar,
+        "u" [B]      Bu . gbar.
+    A and Bu are contracted in registers and never written to memory: one kernel.  Not differentiated: the dynamics
+    parameters, the external forces and dt.  Other arguments as sim_step_jacobian's."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("x", "u") for w in want):
+        raise ValueError("want must name at least one of 'x', 'u'")
+    res = _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, ["g" + w for w in want])
+    return {w: res["g" + w] for w in want}
+
+
+class _SimStepFunction(torch.autograd.Function):
+    """The plant step as a function of (state, u): forward is the simulator's own kernel on a copy, backward one
+    sim_step_vjp call at the saved inputs (sim_step)."""
+
+    @staticmethod
+    def forward(ctx, state, u, params, dt, fext, f_base, f_mass, model):
+        m, nx, npar = _model_dims(model)
+        dtp = state.dtype
+        _require_cuda_tensor(state, "state", dtp)
+        if state.dim() != 2 or state.shape[0] != nx:
+            raise ValueError("state must be [%d, B]" % nx)
+        B = int(state.shape[1])
+        _require_cuda_tensor(u, "u", dtp, (B,))
+        if fext is not None:
+            _require_cuda_tensor(fext, "fext", dtp, (4, B))
+        ctx.args = ([float(v) for v in params], float(dt), None if fext is None else fext.detach().clone(),
+                    tuple(f_base), tuple(f_mass), model)
+        ctx.save_for_backward(state.detach().clone(), u.detach().clone())
+        out = state.detach().clone()
+        shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
+        with torch.cuda.device(state.device):
+            capi.check(capi.load().cpmpc_sim_step_batch_model(m, _CAPI_DTYPE[dtp], B, capi.dbl_array(params, npar),
+                                                              float(dt), _ptr(u), shared, _ptr(fext), _ptr(out),
+                                                              _stream_ptr()))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gbar):
+        state, u = ctx.saved_tensors
+        params, dt, fext, f_base, f_mass, model = ctx.args
+        want = [name for name, i in (("x", 0), ("u", 1)) if ctx.needs_input_grad[i]]
+        res = {}
+        if want:
+            res = sim_step_vjp(params, dt, state, u, gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass, model=model,
+                               want=want)
+        return res.get("x"), res.get("u"), None, None, None, None, None, None
+
+
+def sim_step(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
+    """BatchSimulator.step as a differentiable function: returns the state [nx, B] after dt, bitwise what
+    BatchSimulator.step leaves in a simulator set to `state` (the same kernel, on a copy; `state` is not changed),
+    attached to the autograd graph of state and u.  Backward is one sim_step_vjp call on the current stream at the
+    forward's own copies of (state, u) and is differentiable once only.  Gradients flow to state and u alone: the
+    dynamics parameters, the external forces and dt are not differentiated.  The wrap of the pole angles has unit
+    derivative."""
+    return _SimStepFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
+
+
 class BatchSimulator:
     """B independent pendulum::Simulator plants (optimization/simulator.hpp:10-29)."""
 
@@ -771,6 +880,13 @@ class BatchSimulator:
             capi.check(capi.load().cpmpc_sim_step_batch_model(self.model, _CAPI_DTYPE[self.dtype], B,
                                                               capi.dbl_array(params, self.np), float(dt), _ptr(u),
                                                               shared, _ptr(fext), _ptr(self.state), _stream_ptr()))
+
+    def step_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
+        """step() with a backward: the state after the step is sim_step(params, dt, self.state, u, ...) -- bitwise what
+        step() computes -- becomes self.state and is returned, attached to the autograd graph of the state before the step
+        and of u.  The dynamics parameters, the external forces and dt are not differentiated."""
+        self.state = sim_step(params, dt, self.state, u, fext=fext, f_base=f_base, f_mass=f_mass, model=self.model)
+        return self.state
 
 
 class ClosedLoop:

@@ -779,6 +779,24 @@ extern "C" int cpmpc_linearize_batch(cpmpc_solver* s, int64_t B, const double* d
   return CPMPC_OK;
 }
 
+// simulator.cc:18-22 evaluated in double: the number of sub-steps of a plant step of length dt and the size of the last one
+// (n_sub = 0 for dt = 0).  Shared by the plant step and the plant step with derivatives, so both take the same sub-steps.
+static int sim_sub_steps(double dt, int* n_sub_out, double* h_last_out) {
+  const double internal_dt = 0.001;
+  int n_sub = 0;
+  double h_last = internal_dt;
+  double rem = dt;
+  while (rem > 0.0) {
+    h_last = rem < internal_dt ? rem : internal_dt;
+    ++n_sub;
+    rem -= internal_dt;
+    if (n_sub > 100000000) return fail(CPMPC_ERR_INVALID_ARG, "dt too large");
+  }
+  *n_sub_out = n_sub;
+  *h_last_out = h_last;
+  return CPMPC_OK;
+}
+
 extern "C" int cpmpc_sim_step_batch_model(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
                                           const void* u, const double* fext_host, const void* fext, void* state,
                                           void* stream) {
@@ -786,19 +804,10 @@ extern "C" int cpmpc_sim_step_batch_model(int model, int dtype, int64_t B, const
   if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
   int rc = check_piece_args(model, dtype, B);
   if (rc) return rc;
-  // simulator.cc:18-22 evaluated in double: number of sub-steps and the size of the last one
-  const double internal_dt = 0.001;
   int n_sub = 0;
-  double h_last = internal_dt;
-  {
-    double rem = dt;
-    while (rem > 0.0) {
-      h_last = rem < internal_dt ? rem : internal_dt;
-      ++n_sub;
-      rem -= internal_dt;
-      if (n_sub > 100000000) return fail(CPMPC_ERR_INVALID_ARG, "dt too large");
-    }
-  }
+  double h_last = 0.0;
+  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  if (rc) return rc;
   if (n_sub == 0) return CPMPC_OK;
   engine_for(dtype, model)->sim(B, dyn_shared_host, fext_host, fext, n_sub, h_last, u, state, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
@@ -808,6 +817,51 @@ extern "C" int cpmpc_sim_step_batch(int dtype, int64_t B, const double* dyn_shar
                                     const double* fext_host, const void* fext, void* state, void* stream) {
   return cpmpc_sim_step_batch_model(CPMPC_MODEL_SINGLE, dtype, B, dyn_shared_host, dt, u, fext_host, fext, state,
                                     stream);
+}
+
+// The argument checks of cpmpc_sim_step_jac_batch (no device needed)
+static int check_sim_jac_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, const cpmpc_sim_jac* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_jac)");
+  if (a->struct_size != sizeof(cpmpc_sim_jac))
+    return fail(CPMPC_ERR_INVALID_ARG, "cpmpc_sim_jac.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_sim_jac))",
+                (unsigned long long)a->struct_size, sizeof(cpmpc_sim_jac));
+  if (!dyn_shared_host || !a->state || !a->u) return fail(CPMPC_ERR_INVALID_ARG, "null argument (dyn, state, u)");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  if ((a->gx || a->gu) && !a->gbar) return fail(CPMPC_ERR_INVALID_ARG, "gx / gu are given without gbar");
+  if (a->gbar && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "gbar is given with neither gx nor gu");
+  if (!a->x_new && !a->A && !a->Bu && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
+  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  // the kernel reads a lane's state and cotangent once, before it writes, but another lane's may not have been read yet:
+  // an output that overlaps them is refused
+  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model);
+  const struct { const void* p; size_t rows; const char* name; } outs[3] = {{a->x_new, nx, "x_new"}, {a->gx, nx, "gx"}, {a->A, nx * nx, "A"}};
+  const struct { const void* p; const char* name; } ins[2] = {{a->state, "state"}, {a->gbar, "gbar"}};
+  for (const auto& o : outs)
+    for (const auto& in : ins) {
+      if (!o.p || !in.p) continue;
+      const char *o0 = (const char*)o.p, *i0 = (const char*)in.p;
+      if (o0 < i0 + nx * row && i0 < o0 + o.rows * row)
+        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", o.name, in.name);
+    }
+  return CPMPC_OK;
+}
+
+// Simulator::Step with A = dx+/dx and Bu = dx+/du, or their products with a cotangent (sim_jac_kernels.hpp)
+extern "C" int cpmpc_sim_step_jac_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                                        const cpmpc_sim_jac* a, void* stream) {
+  int rc = check_sim_jac_args(model, dtype, B, dyn_shared_host, dt, a);
+  if (rc) return rc;
+  rc = current_device_ok();
+  if (rc) return rc;
+  int n_sub = 0;
+  double h_last = 0.0;
+  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  if (rc) return rc;
+  engine_for(dtype, model)->sim_jac(B, dyn_shared_host, n_sub, h_last, a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -535,3 +535,44 @@ extern "C" int cpmpc_sim_step_batch_host(int64_t B, const double* dyn_shared_hos
   memcpy(state_host, h, 4 * nB * sizeof(double));
   return CPMPC_OK;
 }
+
+// A = dx+/dx and Bu = dx+/du of the same step with host doubles (pendulum::Simulator::StepJacobian): the staging of the plant
+// step above, [state NX B | u B | A NX NX B | Bu NX B]; one copy in, the kernel, one copy out, one synchronisation.
+extern "C" int cpmpc_sim_step_jac_batch_host(int model, int64_t B, const double* dyn_shared_host, double dt,
+                                             const double* state_host, const double* u_host, const double* fext_host,
+                                             double* A_host, double* Bu_host) {
+  if (!dyn_shared_host || !state_host || !u_host) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  if (!A_host && !Bu_host) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  for (int64_t i = 0; i < B; ++i)
+    if (!std::isfinite(u_host[i])) return fail(CPMPC_ERR_INVALID_ARG, "u = %g is not finite (simulator.cc:14)", u_host[i]);
+  int rc = current_device_ok();
+  if (rc) return rc;
+  const size_t nB = (size_t)B, nx = (size_t)cpmpc_model_state_dim(model);
+  const size_t n_in = (nx + 1) * nB, n_out = (nx * nx + nx) * nB;
+  rc = ensure_sim_stage((n_in + n_out) * sizeof(double));
+  if (rc) return rc;
+  SimStage& g = g_sim_stage;
+  double* h = (double*)g.pin;
+  double* d = (double*)g.dev;
+  memcpy(h, state_host, nx * nB * sizeof(double));
+  memcpy(h + nx * nB, u_host, nB * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(d, h, n_in * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  cpmpc_sim_jac a;
+  memset(&a, 0, sizeof a);
+  a.struct_size = sizeof a;
+  a.state = d;
+  a.u = d + nx * nB;
+  a.fext_host = fext_host;
+  a.A = d + n_in;
+  a.Bu = d + n_in + nx * nx * nB;
+  rc = cpmpc_sim_step_jac_batch(model, CPMPC_F64, B, dyn_shared_host, dt, &a, g.stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h + n_in, d + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIP_TRY(hipStreamSynchronize(g.stream));
+  if (A_host) memcpy(A_host, h + n_in, nx * nx * nB * sizeof(double));
+  if (Bu_host) memcpy(Bu_host, h + n_in + nx * nx * nB, nx * nB * sizeof(double));
+  return CPMPC_OK;
+}

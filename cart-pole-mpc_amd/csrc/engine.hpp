@@ -197,6 +197,10 @@ struct Engine {
               void* x_new, void* A, void* Bm, hipStream_t stream);
   void (*sim)(int64_t B, const double* dyn_shared_host, const double* fext_host, const void* fext, int n_sub,
               double h_last, const void* u, void* state, hipStream_t stream);
+  // the same step from a read-only state, with Phi = dx+/dx and gamma = dx+/du accumulated over its sub-steps
+  // (sim_jac_kernels.hpp): the outputs of `a` that are not null.  n_sub = 0 is the identity map
+  void (*sim_jac)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_jac* a,
+                  hipStream_t stream);
   void (*linearize_batch)(cpmpc_solver* s, int64_t B, const double* dyn_shared_host, const void* z, void* c, void* Phi,
                           void* Gamma, hipStream_t stream);
   // debug builds (-DCPMPC_FUSED_TIMING / -DCPMPC_FUSED_CLOCK): read and clear this unit's counters, ADDING them to out

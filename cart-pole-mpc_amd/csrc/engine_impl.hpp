@@ -13,6 +13,7 @@
 #include "plan_sensitivity_kernels.hpp"
 #include "plan_vjp_kernels.hpp"
 #include "plan_weight_vjp_kernels.hpp"
+#include "sim_jac_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -510,6 +511,13 @@ static void sim_impl(int64_t B, const double* dyn_shared_host, const double* fex
   hipLaunchKernelGGL((sim_kernel<R, M>), grid_for(B), dim3(64), 0, stream, B, M::template make<double>(dyn_shared_host),
                      ext_from_host<R>(fext_host), (const R*)fext, n_sub, (R)h_last, (const R*)u, (R*)state);
 }
+template <typename R, typename M>
+static void sim_jac_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_jac* a,
+                         hipStream_t stream) {
+  hipLaunchKernelGGL((sim_jac_kernel<R, M>), grid_for(B), dim3(64), 0, stream, B, M::template make<double>(dyn_shared_host),
+                     ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, (const R*)a->state,
+                     (const R*)a->u, (R*)a->x_new, (R*)a->A, (R*)a->Bu, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
+}
 
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
@@ -643,6 +651,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
   const Engine* NAME() {                                                                                             \
     static const Engine e = {&step_batch_impl<R, M>, &host_chunk_begin<R, M>, &host_chunk_end<R, M>, &pack_z_impl<R, M>, \
                              &unpack_z_impl<R, M>,   &dynamics_impl<R, M>,   &rk4_impl<R, M>,      &sim_impl<R, M>,    \
+                             &sim_jac_impl<R, M>,                                                                    \
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
                              &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>};                              \

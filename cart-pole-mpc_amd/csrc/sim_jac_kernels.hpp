@@ -1,0 +1,126 @@
+// sim_jac_kernels.hpp -- the plant step with its first derivatives: Simulator::Step (simulator.cc:11-36) as sim_kernel runs
+// it -- 1 ms RK4 sub-steps with the control held, the last one h_last, the pole angles wrapped after each -- together with
+//     Phi = dx+/dx  (NX x NX)  and  gamma = dx+/du  (NX)
+// of the whole step, accumulated FORWARD over the sub-steps as linearize_kernel accumulates an interval:
+//     Phi <- A_i Phi,   gamma <- A_i gamma + B_i,   Phi_0 = I, gamma_0 = 0,
+// with A_i, B_i from rk4_step_jac_m (external forces included).  The wrap has unit derivative.  Nothing per sub-step is
+// stored, whatever their number.  One problem per lane, no LDS; the state is read only.
+//
+// Outputs, each written only where its pointer is given (a wave-uniform choice): x_new [NX][B], A = Phi [NX*NX][B] (element
+// (r, c) at field r*NX + c, the layout of rk4_kernel), Bu = gamma [NX][B] and, for a cotangent gbar [NX][B], the products
+// gx = Phi^T gbar [NX][B] and gu = gamma . gbar [B] contracted in registers.  Derivatives with respect to the state and the
+// control only: none for the dynamics parameters, the external forces or the step length.
+#pragma once
+#include "mpc_kernels.hpp"
+
+namespace cpmpc {
+
+template <typename R, typename M>
+__global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename M::Consts k, ExtForce<R> fe_shared, const R* fext,
+                                                      int n_sub, R h_last, const R* state, const R* u, R* x_new, R* A_out,
+                                                      R* Bu, const R* gbar, R* gx, R* gu) {
+  constexpr int NX = M::NX, NQ = M::NQ;
+  // Columns of every A_i known in closed form (models.hpp: trivial_cols).  Their pattern is closed under the product: column
+  // c of Phi stays e_c, plus the time integrated so far in row c - NQ when c is a velocity -- neither stored nor multiplied.
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= B) return;
+  ExtForce<R> fe = fe_shared;
+  if (fext) {
+    fe.fbx = fext[p];
+    fe.fmx = fext[2 * B + p];
+    fe.fmy = fext[3 * B + p];
+  }
+  R xs[NX];
+#pragma unroll
+  for (int t = 0; t < NX; ++t) xs[t] = state[t * B + p];
+  const R uu = u[p];
+
+  R Phi[NX][NX], gam[NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r) {
+#pragma unroll
+    for (int c = 0; c < NX; ++c)
+      if (!((TRIV >> c) & 1u)) Phi[r][c] = (r == c) ? R(1) : R(0);
+    gam[r] = R(0);
+  }
+  R t_sum = R(0);  // entry (c - NQ, c) of a trivial velocity column: the sub-steps' lengths added up
+
+  const R internal_dt = R(0.001);
+  typename M::StepCache chain;
+#pragma unroll 1
+  for (int i = 0; i < n_sub; ++i) {
+    const R h = (i + 1 == n_sub) ? h_last : internal_dt;
+    R A[NX][NX], Bv[NX];
+    rk4_step_jac_m<R, M, true>(k, h, xs, uu, fe, A, Bv, chain);
+    wrap_angles<R, M>(xs);
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      if ((TRIV >> c) & 1u) continue;
+      R v[NX], y[NX];
+#pragma unroll
+      for (int m = 0; m < NX; ++m) v[m] = Phi[m][c];
+      step_jac_apply<R, M>(A, h, v, y);
+#pragma unroll
+      for (int r = 0; r < NX; ++r) Phi[r][c] = y[r];
+    }
+    {
+      R y[NX];
+      step_jac_apply<R, M>(A, h, gam, y);
+#pragma unroll
+      for (int r = 0; r < NX; ++r) gam[r] = y[r] + Bv[r];
+    }
+    if (TRIV != 0u) t_sum += h;
+  }
+
+  if (x_new)
+#pragma unroll
+    for (int t = 0; t < NX; ++t) x_new[t * B + p] = xs[t];
+  if (A_out)
+#pragma unroll
+    for (int r = 0; r < NX; ++r)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        R v;
+        if ((TRIV >> c) & 1u) v = (r == c) ? R(1) : ((c >= NQ && r == c - NQ) ? t_sum : R(0));  // the closed-form columns
+        else v = Phi[r][c];
+        A_out[(r * NX + c) * B + p] = v;
+      }
+  if (Bu)
+#pragma unroll
+    for (int r = 0; r < NX; ++r) Bu[r * B + p] = gam[r];
+  if (gbar) {
+    R g[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) g[r] = gbar[r * B + p];
+    if (n_sub == 0) {  // the identity map: the cotangent itself, not its products with ones and zeros
+      if (gx)
+#pragma unroll
+        for (int c = 0; c < NX; ++c) gx[c * B + p] = g[c];
+      if (gu) gu[p] = R(0);
+      return;
+    }
+    if (gx)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        R acc;
+        if ((TRIV >> c) & 1u) {
+          acc = g[c];
+          if (c >= NQ) acc += t_sum * g[c - NQ];
+        } else {
+          acc = Phi[0][c] * g[0];
+#pragma unroll
+          for (int r = 1; r < NX; ++r) acc += Phi[r][c] * g[r];
+        }
+        gx[c * B + p] = acc;
+      }
+    if (gu) {
+      R acc = gam[0] * g[0];
+#pragma unroll
+      for (int r = 1; r < NX; ++r) acc += gam[r] * g[r];
+      gu[p] = acc;
+    }
+  }
+}
+
+}  // namespace cpmpc

@@ -219,5 +219,12 @@ PYBIND11_MODULE(pypendulum, m) {
       .def(py::init<>())
       .def("step", &Simulator::Step)
       .def("get_state", &Simulator::GetState)
-      .def("set_state", &Simulator::SetState);
+      .def("set_state", &Simulator::SetState)
+      // (A [4][4] flat row-major, B [4]) of the step at the current state, which is not changed (Simulator::StepJacobian)
+      .def("step_jacobian",
+           [](const Simulator& self, const SingleCartPoleParams& params, double dt, double u, const Vector2& f_base,
+              const Vector2& f_mass) {
+             const auto j = self.StepJacobian(params, dt, u, f_base, f_mass);
+             return py::make_tuple(std::vector<double>(j.A.begin(), j.A.end()), std::vector<double>(j.B.begin(), j.B.end()));
+           });
 }

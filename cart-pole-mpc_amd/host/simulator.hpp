@@ -21,6 +21,17 @@ class Simulator {
 
   void SetState(const SingleCartPoleState& state) noexcept { state_ = state.ToVector(); }
 
+  // The first derivatives of the map Step applies, at the current state (which is not changed): A = dx+/dx row-major
+  // [4][4] and B = dx+/du [4], the control held over dt -- the product of the sub-steps' RK4 Jacobians, the wrap of the pole
+  // angle with unit derivative (include/cpmpc.h: cpmpc_sim_step_jac_batch).  Not differentiated: params, the forces, dt.
+  // Throws as Step.
+  struct StepJacobians {
+    std::array<double, 16> A;
+    std::array<double, 4> B;
+  };
+  [[nodiscard]] StepJacobians StepJacobian(const SingleCartPoleParams& params, double dt, double u, const Vector2& f_base,
+                                           const Vector2& f_mass) const;
+
  private:
   std::array<double, 4> state_{0.0, -3.14159265358979323846 / 2, 0.0, 0.0};  // simulator.hpp:28
 };

@@ -400,6 +400,43 @@ int cpmpc_sim_step_batch_model(int model, int dtype, int64_t B, const double* dy
 int cpmpc_sim_step_batch_host(int64_t B, const double* dyn_shared_host, double dt,
                               const double* u_host, const double* fext_host, double* state_host);
 
+/* ---- the plant step with its first derivatives ----------------------------------------------------------------- */
+/* Simulator::Step as cpmpc_sim_step_batch_model runs it -- the same sub-steps (1 ms, a shorter last one), the control held,
+ * the pole angles wrapped after each -- from a state that is only READ, together with
+ *     A = dx+/dx  [NX*NX][B] (element (r, c) at field r*NX + c, as cpmpc_rk4_batch)   and   Bu = dx+/du  [NX][B]
+ * of the whole step: A <- A_i A, Bu <- A_i Bu + B_i over the sub-steps' RK4 Jacobians A_i, B_i (external forces included;
+ * the wrap has unit derivative), accumulated in registers whatever the number of sub-steps.  With a cotangent gbar [NX][B]
+ * on x+ the call returns gx = A^T gbar [NX][B] and gu = Bu . gbar [B] instead of, or beside, the matrices; A is then never
+ * written to memory.  Every output is nullable, only those given are computed, at least one must be given; gx and gu need
+ * gbar, and gbar needs one of them.  x_new, A and gx must not alias state or gbar.  Each output is bitwise the same
+ * whichever others are asked for with it; x_new agrees with cpmpc_sim_step_batch_model's to rounding, not bitwise (the
+ * step that also forms the Jacobians is compiled separately).  dt = 0: x_new = state, A = I, Bu = 0, gx = gbar, gu = 0.
+ * A problem with a non-finite state has non-finite outputs; no other problem is affected.
+ * What is NOT differentiated: the dynamics parameters, the external forces and dt.
+ * Device pointers in `dtype`; asynchronous on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite,
+ * a wrong struct_size and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_jac {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_jac) */
+  const void* state;      /* [NX][B], read only */
+  const void* u;          /* [B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  void* x_new;            /* [NX][B] or NULL */
+  void* A;                /* [NX*NX][B] or NULL */
+  void* Bu;               /* [NX][B] or NULL */
+  const void* gbar;       /* [NX][B] or NULL */
+  void* gx;               /* [NX][B] or NULL; needs gbar */
+  void* gu;               /* [B] or NULL; needs gbar */
+} cpmpc_sim_jac;
+int cpmpc_sim_step_jac_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                             const cpmpc_sim_jac* a, void* stream);
+/* A and Bu of the same step with HOST doubles (fp64 on the GPU; synchronous; used by the C++ facade,
+ * pendulum::Simulator::StepJacobian): state_host [NX][B] read only, u_host [B], fext_host shared or NULL, A_host
+ * [NX*NX][B] and Bu_host [NX][B], at least one of them given. */
+int cpmpc_sim_step_jac_batch_host(int model, int64_t B, const double* dyn_shared_host, double dt,
+                                  const double* state_host, const double* u_host, const double* fext_host,
+                                  double* A_host /*nullable*/, double* Bu_host /*nullable*/);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
