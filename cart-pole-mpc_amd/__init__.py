@@ -18,7 +18,8 @@ from .capi import CpmpcError, Params, SolverOpts, default_params, default_solver
 def __getattr__(name):
     # torch-dependent pieces are imported lazily so the C-ABI can be inspected without torch
     if name in ("BatchOptimization", "BatchSimulator", "BatchOutputs", "ClosedLoop", "dynamics_batch", "rk4_batch",
-                "feedback_apply", "plan_update", "sim_step_jacobian", "sim_step_vjp", "sim_step"):
+                "feedback_apply", "plan_update", "sim_step_jacobian", "sim_step_vjp", "sim_step",
+                "sim_step_param_jacobian", "sim_step_param_vjp"):
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

@@ -777,7 +777,8 @@ def sim_step_jacobian(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass
         "A"     [nx, nx, B]  dx+/dx,
         "Bu"    [nx, B]      dx+/du, the control held over the step,
     the product of the sub-steps' RK4 Jacobians.  params, dt, f_base / f_mass / fext as BatchSimulator.step's.  Not
-    differentiated: the dynamics parameters, the external forces and dt.  Only what is named is computed."""
+    differentiated here: the dynamics parameters (sim_step_param_jacobian does that), the external forces and dt.  Only
+    what is named is computed."""
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in ("x_new", "A", "Bu") for w in want):
         raise ValueError("want must name at least one of 'x_new', 'A', 'Bu'")
@@ -790,8 +791,8 @@ def sim_step_vjp(params, dt, state, u, gbar, fext=None, f_base=(0.0, 0.0), f_mas
     the inputs named in `want` -- a dict with
         "x" [nx, B]  A^T gbar,
         "u" [B]      Bu . gbar.
-    A and Bu are contracted in registers and never written to memory: one kernel.  Not differentiated: the dynamics
-    parameters, the external forces and dt.  Other arguments as sim_step_jacobian's."""
+    A and Bu are contracted in registers and never written to memory: one kernel.  Not differentiated here: the dynamics
+    parameters (sim_step_param_vjp does that), the external forces and dt.  Other arguments as sim_step_jacobian's."""
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or any(w not in ("x", "u") for w in want):
         raise ValueError("want must name at least one of 'x', 'u'")
@@ -799,9 +800,96 @@ def sim_step_vjp(params, dt, state, u, gbar, fext=None, f_base=(0.0, 0.0), f_mas
     return {w: res["g" + w] for w in want}
 
 
+def _dyn_arg(params, npar, dtp, B):
+    """-> (shared host array or None, device pointer or None) of a parameter set given as npar floats or as an [npar, B] tensor."""
+    if isinstance(params, torch.Tensor):
+        _require_cuda_tensor(params, "params", dtp, (npar, B))
+        return None, params.data_ptr()
+    return capi.dbl_array(params, npar), None
+
+
+def _plant_step(model, npar, dtp, B, params, dt, u, shared, fext, state):
+    """The plant step in place on `state`: npar floats -> cpmpc_sim_step_batch_model, as ever; an [npar, B] tensor ->
+    cpmpc_sim_step_dyn_batch (per-problem parameters)."""
+    if isinstance(params, torch.Tensor):
+        _require_cuda_tensor(params, "params", dtp, (npar, B))
+        capi.check(capi.load().cpmpc_sim_step_dyn_batch(model, _CAPI_DTYPE[dtp], B, None, _ptr(params), float(dt), _ptr(u),
+                                                        shared, _ptr(fext), _ptr(state), _stream_ptr()))
+    else:
+        capi.check(capi.load().cpmpc_sim_step_batch_model(model, _CAPI_DTYPE[dtp], B, capi.dbl_array(params, npar),
+                                                          float(dt), _ptr(u), shared, _ptr(fext), _ptr(state),
+                                                          _stream_ptr()))
+
+
+def _sim_param_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, names):
+    """One cpmpc_sim_step_param_jac_batch call on the current stream for the outputs in `names` (fields of
+    cpmpc_sim_param_jac)."""
+    m, nx, npar = _model_dims(model)
+    dtp = state.dtype
+    _require_cuda_tensor(state, "state", dtp)
+    if state.dim() != 2 or state.shape[0] != nx:
+        raise ValueError("state must be [%d, B]" % nx)
+    B = int(state.shape[1])
+    _require_cuda_tensor(u, "u", dtp, (B,))
+    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)   # read by the call itself, before it returns
+    a = capi.SimParamJac(struct_size=C.sizeof(capi.SimParamJac))
+    a.state, a.u = state.data_ptr(), u.data_ptr()
+    a.fext_host = C.cast(shared, C.POINTER(C.c_double))
+    if fext is not None:
+        _require_cuda_tensor(fext, "fext", dtp, (4, B))
+        a.fext = fext.data_ptr()
+    if gbar is not None:
+        _require_cuda_tensor(gbar, "gbar", dtp, (nx, B))
+        a.gbar = gbar.data_ptr()
+    host, dev = _dyn_arg(params, npar, dtp, B)
+    if dev is not None:
+        a.dyn = dev
+    shapes = {"x_new": (nx, B), "P": (nx, npar, B), "gp": (npar, B), "gx": (nx, B), "gu": (B,)}
+    res = {}
+    for name in names:
+        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
+        setattr(a, name, res[name].data_ptr())
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_step_param_jac_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), C.byref(a),
+                                                              _stream_ptr()))
+    return res
+
+
+def sim_step_param_jacobian(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+                            want=("x_new", "P")):
+    """The plant step's derivative in the dynamics parameters (include/cpmpc.h: cpmpc_sim_step_param_jac_batch): for state
+    [nx, B] (read, not changed) and u [B] a dict with the entries named in `want`,
+        "x_new" [nx, B]      the state after dt,
+        "P"     [nx, np, B]  dx+/dp, p in the order of the parameter vector (9 numbers for the 4-state model, 6 for the
+                             6-state one).
+    params: np floats (one plant for all) or an [np, B] tensor (a plant per problem).  First derivatives of the accelerations
+    only; the control and the external forces are held, the wrap has unit derivative.  Not differentiated: the external
+    forces and dt."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("x_new", "P") for w in want):
+        raise ValueError("want must name at least one of 'x_new', 'P'")
+    return _sim_param_call(params, dt, state, u, fext, f_base, f_mass, model, None, want)
+
+
+def sim_step_param_vjp(params, dt, state, u, gbar, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+                       want=("p", "x", "u")):
+    """The reverse mode of sim_step_param_jacobian and sim_step_jacobian in one call: a cotangent gbar = dL/dx+ [nx, B]
+    pulled back to the inputs named in `want` -- a dict with
+        "p" [np, B]  P^T gbar (per problem, also where params is one shared set: sum over the batch for its gradient),
+        "x" [nx, B]  A^T gbar,
+        "u" [B]      Bu . gbar.
+    P, A and Bu are contracted in registers and never written to memory.  params as sim_step_param_jacobian's."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("p", "x", "u") for w in want):
+        raise ValueError("want must name at least one of 'p', 'x', 'u'")
+    res = _sim_param_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, ["g" + w for w in want])
+    return {w: res["g" + w] for w in want}
+
+
 class _SimStepFunction(torch.autograd.Function):
-    """The plant step as a function of (state, u): forward is the simulator's own kernel on a copy, backward one
-    sim_step_vjp call at the saved inputs (sim_step)."""
+    """The plant step as a function of (state, u) and, where params is a tensor, of the parameters: forward is the
+    simulator's own kernel on a copy, backward one sim_step_vjp (or, with a params tensor, sim_step_param_vjp) call at the
+    saved inputs (sim_step)."""
 
     @staticmethod
     def forward(ctx, state, u, params, dt, fext, f_base, f_mass, model):
@@ -814,15 +902,16 @@ class _SimStepFunction(torch.autograd.Function):
         _require_cuda_tensor(u, "u", dtp, (B,))
         if fext is not None:
             _require_cuda_tensor(fext, "fext", dtp, (4, B))
-        ctx.args = ([float(v) for v in params], float(dt), None if fext is None else fext.detach().clone(),
-                    tuple(f_base), tuple(f_mass), model)
+        per_problem = isinstance(params, torch.Tensor)
+        if per_problem:
+            _require_cuda_tensor(params, "params", dtp, (npar, B))
+        ctx.args = (params.detach().clone() if per_problem else [float(v) for v in params], float(dt),
+                    None if fext is None else fext.detach().clone(), tuple(f_base), tuple(f_mass), model)
         ctx.save_for_backward(state.detach().clone(), u.detach().clone())
         out = state.detach().clone()
         shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
         with torch.cuda.device(state.device):
-            capi.check(capi.load().cpmpc_sim_step_batch_model(m, _CAPI_DTYPE[dtp], B, capi.dbl_array(params, npar),
-                                                              float(dt), _ptr(u), shared, _ptr(fext), _ptr(out),
-                                                              _stream_ptr()))
+            _plant_step(m, npar, dtp, B, params.detach() if per_problem else params, dt, u, shared, fext, out)
         return out
 
     @staticmethod
@@ -832,6 +921,13 @@ class _SimStepFunction(torch.autograd.Function):
         params, dt, fext, f_base, f_mass, model = ctx.args
         want = [name for name, i in (("x", 0), ("u", 1)) if ctx.needs_input_grad[i]]
         res = {}
+        if isinstance(params, torch.Tensor):   # per-problem parameters: one call for every gradient asked for
+            if ctx.needs_input_grad[2]:
+                want = ["p"] + want
+            if want:
+                res = sim_step_param_vjp(params, dt, state, u, gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass,
+                                         model=model, want=want)
+            return res.get("x"), res.get("u"), res.get("p"), None, None, None, None, None
         if want:
             res = sim_step_vjp(params, dt, state, u, gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass, model=model,
                                want=want)
@@ -842,9 +938,13 @@ def sim_step(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.
     """BatchSimulator.step as a differentiable function: returns the state [nx, B] after dt, bitwise what
     BatchSimulator.step leaves in a simulator set to `state` (the same kernel, on a copy; `state` is not changed),
     attached to the autograd graph of state and u.  Backward is one sim_step_vjp call on the current stream at the
-    forward's own copies of (state, u) and is differentiable once only.  Gradients flow to state and u alone: the
-    dynamics parameters, the external forces and dt are not differentiated.  The wrap of the pole angles has unit
-    derivative."""
+    forward's own copies of (state, u) and is differentiable once only.  The wrap of the pole angles has unit derivative.
+
+    params: np floats -- gradients flow to state and u alone, everything bitwise as before -- or an [np, B] tensor of
+    per-problem parameters (cpmpc_sim_step_dyn_batch).  When that tensor requires grad, backward makes one
+    sim_step_param_vjp call and returns dL/dp [np, B] for it beside the gradients for state and u.  A SHARED parameter
+    set that should receive a gradient is passed as p.expand(np, B).contiguous() of an [np, 1] tensor p by the caller:
+    autograd then sums the per-problem gradients over the batch.  The external forces and dt are not differentiated."""
     return _SimStepFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
 
 
@@ -870,21 +970,22 @@ class BatchSimulator:
 
     def step(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """u: [B] tensor.  f_base/f_mass shared (x, y) pairs, or fext a [4, B] tensor
-        {f_base.x, f_base.y, f_mass.x, f_mass.y}."""
+        {f_base.x, f_base.y, f_mass.x, f_mass.y}.  params: np floats (one plant for all), or an [np, B] tensor: a plant
+        per problem (cpmpc_sim_step_dyn_batch)."""
         B = int(self.state.shape[1])
         _require_cuda_tensor(u, "u", self.dtype, (B,))
         shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
         if fext is not None:
             _require_cuda_tensor(fext, "fext", self.dtype, (4, B))
         with torch.cuda.device(self.device):
-            capi.check(capi.load().cpmpc_sim_step_batch_model(self.model, _CAPI_DTYPE[self.dtype], B,
-                                                              capi.dbl_array(params, self.np), float(dt), _ptr(u),
-                                                              shared, _ptr(fext), _ptr(self.state), _stream_ptr()))
+            _plant_step(self.model, self.np, self.dtype, B, params.detach() if isinstance(params, torch.Tensor) else params,
+                        dt, u, shared, fext, self.state)
 
     def step_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """step() with a backward: the state after the step is sim_step(params, dt, self.state, u, ...) -- bitwise what
         step() computes -- becomes self.state and is returned, attached to the autograd graph of the state before the step
-        and of u.  The dynamics parameters, the external forces and dt are not differentiated."""
+        and of u -- and of params, where that is an [np, B] tensor requiring grad (sim_step).  The external forces and dt
+        are not differentiated."""
         self.state = sim_step(params, dt, self.state, u, fext=fext, f_base=f_base, f_mass=f_mass, model=self.model)
         return self.state
 
@@ -961,22 +1062,26 @@ class ClosedLoop:
         st = self.streams[i]
         return torch.cuda.stream(st) if st is not None else torch.cuda.stream(torch.cuda.current_stream(self.device))
 
-    def tick(self, dyn, set_point=0.0, dt=0.01, want_stats=True, substeps=1, fext=None, set_point_inner=None):
+    def tick(self, dyn, set_point=0.0, dt=0.01, want_stats=True, substeps=1, fext=None, set_point_inner=None, plant_dyn=None):
         """One MPC tick of every controller (queued, not waited for).  With feedback=True the plant advances in `substeps`
         steps of dt / substeps, each under u_0 + K[0] . wrap(x - x0) of its current state; fext: optional callable
         (range index, sub-step) -> [4, n] tensor of external forces on that range's plants for that sub-step.
         set_point_inner (feedback=True; a float or a [B] tensor): the set-point as it stands during the sub-steps, where it
         has moved since the plan was made for `set_point`; the sub-steps then apply
-        u_0 + K[0] . wrap(x - x0) + k_sp[0] (set_point_inner - set_point) (BatchOptimization.plan_sensitivity)."""
+        u_0 + K[0] . wrap(x - x0) + k_sp[0] (set_point_inner - set_point) (BatchOptimization.plan_sensitivity).
+        plant_dyn: the PLANTS' parameters where they differ from what the controllers believe (`dyn`): np floats, or an
+        [np, B] tensor, a plant per problem, split over the ranges as the states are (model mismatch, domain
+        randomisation).  With plant_dyn given, dyn may be an [np, B] tensor too (per-problem controllers); without it dyn
+        is the plants' parameter set as well and must be the np numbers."""
         if not self.feedback and (int(substeps) != 1 or fext is not None or set_point_inner is not None):
             raise ValueError("ClosedLoop.tick: substeps / fext / set_point_inner belong to the feedback loop "
                              "(ClosedLoop(..., feedback=True))")
         if int(substeps) < 1:
             raise ValueError("substeps must be >= 1")
-        if isinstance(dyn, torch.Tensor):
+        if isinstance(dyn, torch.Tensor) and plant_dyn is None:
             raise TypeError("ClosedLoop.tick: dyn is the plant's parameter set too (cpmpc_sim_step_batch takes shared host "
                             "parameters): pass the %d numbers, not a tensor" % self.sims[0].np)
-        tensors = [t for t in (set_point, set_point_inner) if isinstance(t, torch.Tensor)]
+        tensors = [t for t in (set_point, set_point_inner, plant_dyn, dyn) if isinstance(t, torch.Tensor)]
         if len(self.sims) > 1 and (self._inputs_dirty or tensors):
             # whatever prepared the states -- or this tick's per-problem parameters / set-points -- on the caller's stream
             # comes first.  Shared (host) parameters and no set_state since the last tick: no wait, the ranges run free.
@@ -992,21 +1097,26 @@ class ClosedLoop:
             with self._on(i):
                 # per-problem set-points [B]: this range's columns (copied on the range's stream)
                 sp = set_point if one or not isinstance(set_point, torch.Tensor) else set_point[lo:hi].contiguous()
+                dyn_i = dyn if one or not isinstance(dyn, torch.Tensor) else dyn[:, lo:hi].contiguous()
+                pd = dyn_i if plant_dyn is None else plant_dyn
+                if isinstance(pd, torch.Tensor) and not one and plant_dyn is not None:
+                    pd = pd[:, lo:hi].contiguous()
                 if self.feedback:
                     spi = set_point_inner
                     if isinstance(spi, torch.Tensor) and not one:
                         spi = spi[lo:hi].contiguous()
-                    self._tick_feedback(i, s, o, out, dyn, sp, dt, want_stats, int(substeps), fext, spi)
+                    self._tick_feedback(i, s, o, out, dyn_i, sp, dt, want_stats, int(substeps), fext, spi, pd)
                     continue
-                r = o.step(s.get_state(), dyn, sp, want_predicted=False, want_stats=want_stats, out=out)
-                s.step(dyn, dt, r.u[0].contiguous())
+                r = o.step(s.get_state(), dyn_i, sp, want_predicted=False, want_stats=want_stats, out=out)
+                s.step(pd, dt, r.u[0].contiguous())
         self.ticks += 1
 
-    def _tick_feedback(self, i, s, o, out, dyn, sp, dt, want_stats, substeps, fext, sp_inner=None):
+    def _tick_feedback(self, i, s, o, out, dyn, sp, dt, want_stats, substeps, fext, sp_inner=None, plant_dyn=None):
+        plant_dyn = dyn if plant_dyn is None else plant_dyn   # the plants' parameters (tick: plant_dyn)
         x0 = s.get_state().clone()  # the state the plan is made for: the plant's own tensor moves under the sub-steps
         r = o.step(x0, dyn, sp, want_predicted=False, want_stats=want_stats, out=out)
         if sp_inner is not None:
-            self._substeps_with_set_point(i, s, o, r, x0, dyn, sp, sp_inner, dt, substeps, fext)
+            self._substeps_with_set_point(i, s, o, r, x0, dyn, sp, sp_inner, dt, substeps, fext, plant_dyn)
             return
         K, ok = o.feedback_gain(dyn, n_rows=1, want_ok=True)
         # a controller whose QP is not positive definite has no gain (NaN rows): it holds the plan's u_0, as the plain loop does
@@ -1014,13 +1124,14 @@ class ClosedLoop:
         u_nom = r.u[0].contiguous()
         for m in range(substeps):
             u = feedback_apply(u_nom, K0, x0, s.get_state(), u_limit=self.u_limit, model=self.model)
-            s.step(dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
+            s.step(plant_dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
         self.applied[i] = u  # the control of the last sub-step
 
-    def _substeps_with_set_point(self, i, s, o, r, x0, dyn, sp, sp_inner, dt, substeps, fext):
+    def _substeps_with_set_point(self, i, s, o, r, x0, dyn, sp, sp_inner, dt, substeps, fext, plant_dyn=None):
         """The sub-steps of a tick whose set-point has moved since the plan: K[0] and k_sp[0] from one call, applied by
         plan_update on row 0.  A lane with ok = 0 holds the plan's u_0."""
         n = int(x0.shape[1])
+        plant_dyn = dyn if plant_dyn is None else plant_dyn
 
         def per_problem(v):
             return v if isinstance(v, torch.Tensor) else torch.full((n,), float(v), dtype=self.dtype, device=x0.device)
@@ -1033,7 +1144,7 @@ class ClosedLoop:
         for m in range(substeps):
             u = plan_update(u_nom, K=K, x_nom=x0, x=s.get_state(), k_sp=k_sp, sp_nom=sp_nom, sp=sp_now,
                             u_limit=self.u_limit, model=self.model)[0]
-            s.step(dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
+            s.step(plant_dyn, dt / substeps, u, fext=None if fext is None else fext(i, m))
         self.applied[i] = u  # the control of the last sub-step
 
     def synchronize(self):

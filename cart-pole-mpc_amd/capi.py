@@ -49,6 +49,7 @@ SYMBOLS = [
     "cpmpc_plan_vjp_batch", "cpmpc_plan_vjp_batch_host",
     "cpmpc_plan_weight_vjp_batch", "cpmpc_plan_weight_vjp_batch_host",
     "cpmpc_sim_step_jac_batch", "cpmpc_sim_step_jac_batch_host",
+    "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
 ]
 
 
@@ -233,6 +234,25 @@ class SimJac(C.Structure):
     ]
 
 
+class SimParamJac(C.Structure):
+    """cpmpc_sim_param_jac: device pointers of cpmpc_sim_step_param_jac_batch; state, u and dyn are read, every output is
+    nullable, gp, gx and gu need gbar."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("state", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("x_new", C.c_void_p),
+        ("P", C.c_void_p),
+        ("gbar", C.c_void_p),
+        ("gp", C.c_void_p),
+        ("gx", C.c_void_p),
+        ("gu", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -360,6 +380,9 @@ def load():
     L.cpmpc_plan_weight_vjp_batch_host.argtypes = [vp, i64, C.POINTER(WeightVjpInputs), i32, _dp, _dp, _dp, _dp, _dp, _ip]
     L.cpmpc_sim_step_jac_batch.argtypes = [i32, i32, i64, _dp, dbl, C.POINTER(SimJac), vp]
     L.cpmpc_sim_step_jac_batch_host.argtypes = [i32, i64, _dp, dbl, _dp, _dp, _dp, _dp, _dp]
+    L.cpmpc_sim_step_dyn_batch.argtypes = [i32, i32, i64, _dp, vp, dbl, vp, _dp, vp, vp, vp]
+    L.cpmpc_sim_step_param_jac_batch.argtypes = [i32, i32, i64, _dp, dbl, C.POINTER(SimParamJac), vp]
+    L.cpmpc_sim_step_param_jac_batch_host.argtypes = [i32, i64, _dp, dbl, _dp, _dp, _dp, _dp, _dp]
     _lib = L
     return L
 

@@ -864,6 +864,83 @@ extern "C" int cpmpc_sim_step_jac_batch(int model, int dtype, int64_t B, const d
   return CPMPC_OK;
 }
 
+// The plant step with per-problem parameters: dyn == NULL is cpmpc_sim_step_batch_model itself
+extern "C" int cpmpc_sim_step_dyn_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, const void* dyn,
+                                        double dt, const void* u, const double* fext_host, const void* fext, void* state,
+                                        void* stream) {
+  if (!dyn) return cpmpc_sim_step_batch_model(model, dtype, B, dyn_shared_host, dt, u, fext_host, fext, state, stream);
+  if (!u || !state) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
+  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  {  // the kernel updates the state in place while other lanes still read their parameters
+    const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4);
+    const char *s0 = (const char*)state, *d0 = (const char*)dyn;
+    if (s0 < d0 + (size_t)cpmpc_model_num_params(model) * row && d0 < s0 + (size_t)model_nx(model) * row)
+      return fail(CPMPC_ERR_INVALID_ARG, "state overlaps dyn, which the call only reads (give another array)");
+  }
+  int rc = current_device_ok();
+  if (rc) return rc;
+  int n_sub = 0;
+  double h_last = 0.0;
+  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  if (rc) return rc;
+  if (n_sub == 0) return CPMPC_OK;
+  engine_for(dtype, model)->sim_dyn(B, dyn, fext_host, fext, n_sub, h_last, u, state, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
+}
+
+// The argument checks of cpmpc_sim_step_param_jac_batch (no device needed)
+static int check_sim_param_jac_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                                    const cpmpc_sim_param_jac* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_param_jac)");
+  if (a->struct_size != sizeof(cpmpc_sim_param_jac))
+    return fail(CPMPC_ERR_INVALID_ARG,
+                "cpmpc_sim_param_jac.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_sim_param_jac))",
+                (unsigned long long)a->struct_size, sizeof(cpmpc_sim_param_jac));
+  if (!a->state || !a->u) return fail(CPMPC_ERR_INVALID_ARG, "null argument (state, u)");
+  if (!dyn_shared_host && !a->dyn) return fail(CPMPC_ERR_INVALID_ARG, "null argument (neither dyn_shared_host nor dyn is given)");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  if ((a->gp || a->gx || a->gu) && !a->gbar) return fail(CPMPC_ERR_INVALID_ARG, "gp / gx / gu are given without gbar");
+  if (a->gbar && !a->gp && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "gbar is given with none of gp, gx, gu");
+  if (!a->x_new && !a->P && !a->gp && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
+  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  // lanes run in any order: an output that overlaps what another lane has yet to read is refused
+  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model);
+  const size_t np = (size_t)cpmpc_model_num_params(model);
+  const struct { const void* p; size_t rows; const char* name; } outs[5] = {
+      {a->x_new, nx, "x_new"}, {a->P, nx * np, "P"}, {a->gp, np, "gp"}, {a->gx, nx, "gx"}, {a->gu, 1, "gu"}};
+  const struct { const void* p; size_t rows; const char* name; } ins[3] = {{a->state, nx, "state"}, {a->gbar, nx, "gbar"}, {a->dyn, np, "dyn"}};
+  for (const auto& o : outs)
+    for (const auto& in : ins) {
+      if (!o.p || !in.p) continue;
+      const char *o0 = (const char*)o.p, *i0 = (const char*)in.p;
+      if (o0 < i0 + in.rows * row && i0 < o0 + o.rows * row)
+        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", o.name, in.name);
+    }
+  return CPMPC_OK;
+}
+
+// Simulator::Step with P = dx+/dp, or its product with a cotangent, and the state / control cotangents (sim_param_kernels.hpp)
+extern "C" int cpmpc_sim_step_param_jac_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                                              const cpmpc_sim_param_jac* a, void* stream) {
+  int rc = check_sim_param_jac_args(model, dtype, B, dyn_shared_host, dt, a);
+  if (rc) return rc;
+  rc = current_device_ok();
+  if (rc) return rc;
+  int n_sub = 0;
+  double h_last = 0.0;
+  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  if (rc) return rc;
+  engine_for(dtype, model)->sim_param_jac(B, dyn_shared_host, n_sub, h_last, a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

@@ -576,3 +576,43 @@ extern "C" int cpmpc_sim_step_jac_batch_host(int model, int64_t B, const double*
   if (Bu_host) memcpy(Bu_host, h + n_in + nx * nx * nB, nx * nB * sizeof(double));
   return CPMPC_OK;
 }
+
+// P = dx+/dp (and x+) of the same step with host doubles and the shared parameter set (pendulum::Simulator::StepParamJacobian):
+// the same staging, [state NX B | u B | P NX NP B | x_new NX B].
+extern "C" int cpmpc_sim_step_param_jac_batch_host(int model, int64_t B, const double* dyn_shared_host, double dt,
+                                                   const double* state_host, const double* u_host, const double* fext_host,
+                                                   double* P_host, double* x_new_host) {
+  if (!dyn_shared_host || !state_host || !u_host || !P_host) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  for (int64_t i = 0; i < B; ++i)
+    if (!std::isfinite(u_host[i])) return fail(CPMPC_ERR_INVALID_ARG, "u = %g is not finite (simulator.cc:14)", u_host[i]);
+  int rc = current_device_ok();
+  if (rc) return rc;
+  const size_t nB = (size_t)B, nx = (size_t)cpmpc_model_state_dim(model), np = (size_t)cpmpc_model_num_params(model);
+  const size_t n_in = (nx + 1) * nB, n_out = (nx * np + nx) * nB;
+  rc = ensure_sim_stage((n_in + n_out) * sizeof(double));
+  if (rc) return rc;
+  SimStage& g = g_sim_stage;
+  double* h = (double*)g.pin;
+  double* d = (double*)g.dev;
+  memcpy(h, state_host, nx * nB * sizeof(double));
+  memcpy(h + nx * nB, u_host, nB * sizeof(double));
+  HIP_TRY(hipMemcpyAsync(d, h, n_in * sizeof(double), hipMemcpyHostToDevice, g.stream));
+  cpmpc_sim_param_jac a;
+  memset(&a, 0, sizeof a);
+  a.struct_size = sizeof a;
+  a.state = d;
+  a.u = d + nx * nB;
+  a.fext_host = fext_host;
+  a.P = d + n_in;
+  a.x_new = d + n_in + nx * np * nB;
+  rc = cpmpc_sim_step_param_jac_batch(model, CPMPC_F64, B, dyn_shared_host, dt, &a, g.stream);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h + n_in, d + n_in, n_out * sizeof(double), hipMemcpyDeviceToHost, g.stream));
+  HIP_TRY(hipStreamSynchronize(g.stream));
+  memcpy(P_host, h + n_in, nx * np * nB * sizeof(double));
+  if (x_new_host) memcpy(x_new_host, h + n_in + nx * np * nB, nx * nB * sizeof(double));
+  return CPMPC_OK;
+}

@@ -228,6 +228,14 @@ struct Engine {
   // linearisation scratch and the rows of W and T only
   void (*plan_weight_vjp)(cpmpc_solver* s, int64_t B, const cpmpc_weight_vjp_inputs* in, int n_rows, const void* gbar,
                           void* g_tw, void* g_wu, void* g_wdu, void* du, int32_t* ok, hipStream_t stream);
+  // the plant step with per-problem parameters dyn [NP][B] (sim_kernel's PER_LANE instantiation)
+  void (*sim_dyn)(int64_t B, const void* dyn, const double* fext_host, const void* fext, int n_sub, double h_last,
+                  const void* u, void* state, hipStream_t stream);
+  // the plant step with P = dx+/dp, or gp = P^T gbar, in groups of parameter columns (sim_param_kernels.hpp), and the
+  // state / control cotangents gx, gu of sim_jac_kernel with shared or per-problem parameters: the outputs of `a` that are
+  // not null
+  void (*sim_param_jac)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_param_jac* a,
+                        hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

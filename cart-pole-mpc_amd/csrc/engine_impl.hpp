@@ -14,6 +14,7 @@
 #include "plan_vjp_kernels.hpp"
 #include "plan_weight_vjp_kernels.hpp"
 #include "sim_jac_kernels.hpp"
+#include "sim_param_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -519,6 +520,63 @@ static void sim_jac_impl(int64_t B, const double* dyn_shared_host, int n_sub, do
                      (const R*)a->u, (R*)a->x_new, (R*)a->A, (R*)a->Bu, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
 }
 
+// ---- per-problem plant parameters, and the plant step's derivative in them (sim_param_kernels.hpp) ---------------------
+// dyn [NP][B] on the device: the PER_LANE instantiations of the two plant kernels
+template <typename R, typename M>
+static void sim_dyn_impl(int64_t B, const void* dyn, const double* fext_host, const void* fext, int n_sub, double h_last,
+                         const void* u, void* state, hipStream_t stream) {
+  hipLaunchKernelGGL((sim_kernel<R, M, true>), grid_for(B), dim3(64), 0, stream, B, (const R*)dyn, ext_from_host<R>(fext_host),
+                     (const R*)fext, n_sub, (R)h_last, (const R*)u, (R*)state);
+}
+
+// Width of a group of parameter columns of sim_param_jac_kernel: the largest for which no instantiation of the unit has
+// scratch (-Rpass-analysis=kernel-resource-usage under the unit's flags; the table is in DESIGN.md 5f).  That is every
+// column for all four (dtype, model) pairs, so a call is one launch; a pair that ever needs scratch specialises this.
+template <typename R, typename M>
+struct ParamGroupWidth {
+  static constexpr int value = M::NP;
+};
+
+template <typename R, typename M, int J0, bool PER_LANE>
+static void launch_param_groups(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_param_jac* a,
+                                hipStream_t stream) {
+  constexpr int W = ParamGroupWidth<R, M>::value;
+  constexpr int NG = (J0 + W <= M::NP) ? W : M::NP - J0;
+  R* x_new = (J0 == 0) ? (R*)a->x_new : nullptr;  // the primal step is every group's; the first one writes it
+  if (x_new || a->P || a->gp) {
+    typename M::Consts k{};
+    RawParams<R, M::NP> raw{};
+    if constexpr (!PER_LANE) {
+      k = M::template make<double>(dyn_shared_host);
+      for (int i = 0; i < M::NP; ++i) raw.p[i] = (R)dyn_shared_host[i];
+    }
+    hipLaunchKernelGGL((sim_param_jac_kernel<R, M, J0, NG, PER_LANE>), grid_for(B), dim3(64), 0, stream, B, k, raw,
+                       (const R*)a->dyn, ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last,
+                       (const R*)a->state, (const R*)a->u, x_new, (R*)a->P, (const R*)(a->gp ? a->gbar : nullptr), (R*)a->gp);
+  }
+  if constexpr (J0 + NG < M::NP) launch_param_groups<R, M, J0 + NG, PER_LANE>(B, dyn_shared_host, n_sub, h_last, a, stream);
+}
+
+// gx / gu: sim_jac_kernel (the shared set: the instantiation cpmpc_sim_step_jac_batch launches); x_new, P, gp: the groups
+template <typename R, typename M>
+static void sim_param_jac_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_param_jac* a,
+                               hipStream_t stream) {
+  if (a->gx || a->gu) {
+    if (a->dyn)
+      hipLaunchKernelGGL((sim_jac_kernel<R, M, true>), grid_for(B), dim3(64), 0, stream, B, (const R*)a->dyn,
+                         ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, (const R*)a->state,
+                         (const R*)a->u, (R*)nullptr, (R*)nullptr, (R*)nullptr, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
+    else
+      hipLaunchKernelGGL((sim_jac_kernel<R, M>), grid_for(B), dim3(64), 0, stream, B, M::template make<double>(dyn_shared_host),
+                         ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, (const R*)a->state,
+                         (const R*)a->u, (R*)nullptr, (R*)nullptr, (R*)nullptr, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
+  }
+  if (a->x_new || a->P || a->gp) {
+    if (a->dyn) launch_param_groups<R, M, 0, true>(B, dyn_shared_host, n_sub, h_last, a, stream);
+    else launch_param_groups<R, M, 0, false>(B, dyn_shared_host, n_sub, h_last, a, stream);
+  }
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
 // linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
@@ -654,6 +712,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
                              &sim_jac_impl<R, M>,                                                                    \
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
-                             &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>};                              \
+                             &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>, &sim_dyn_impl<R, M>,           \
+                             &sim_param_jac_impl<R, M>};                                                             \
     return &e;                                                                                                       \
   }

@@ -1346,13 +1346,32 @@ __global__ __launch_bounds__(64) void rk4_kernel(int64_t B, typename M::Consts k
   for (int t = 0; t < NX; ++t) xn[t * B + p] = xs[t];
 }
 
-// Simulator::Step (simulator.cc:11-36): fixed 1 ms sub-steps, angles wrapped after each.
+// The plant kernels' dynamics constants: the shared set's, folded on the host (a kernel argument, as it has always been), or
+// -- PER_LANE -- per-problem parameters dyn [NP][B], read by each lane and folded in the kernel as load_consts does.
+template <typename R, typename M, bool PER_LANE>
+struct PlantConsts {
+  using Arg = typename M::Consts;
+  __device__ __forceinline__ static const Arg& get(const Arg& k, int64_t, int64_t) { return k; }
+};
 template <typename R, typename M>
-__global__ __launch_bounds__(64) void sim_kernel(int64_t B, typename M::Consts k, ExtForce<R> fe_shared,
+struct PlantConsts<R, M, true> {
+  using Arg = const R*;
+  __device__ __forceinline__ static typename M::Consts get(const R* dyn, int64_t B, int64_t p) {
+    R prm[M::NP];
+#pragma unroll
+    for (int i = 0; i < M::NP; ++i) prm[i] = dyn[i * B + p];
+    return M::template make<R>(prm);
+  }
+};
+
+// Simulator::Step (simulator.cc:11-36): fixed 1 ms sub-steps, angles wrapped after each.
+template <typename R, typename M, bool PER_LANE = false>
+__global__ __launch_bounds__(64) void sim_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg, ExtForce<R> fe_shared,
                                                   const R* fext, int n_sub, R h_last, const R* u, R* state) {
   constexpr int NX = M::NX;
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B) return;
+  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
   ExtForce<R> fe = fe_shared;
   if (fext) {
     fe.fbx = fext[p];

@@ -9,14 +9,16 @@
 // Outputs, each written only where its pointer is given (a wave-uniform choice): x_new [NX][B], A = Phi [NX*NX][B] (element
 // (r, c) at field r*NX + c, the layout of rk4_kernel), Bu = gamma [NX][B] and, for a cotangent gbar [NX][B], the products
 // gx = Phi^T gbar [NX][B] and gu = gamma . gbar [B] contracted in registers.  Derivatives with respect to the state and the
-// control only: none for the dynamics parameters, the external forces or the step length.
+// control only: the dynamics parameters have sim_param_kernels.hpp; none for the external forces or the step length.
 #pragma once
 #include "mpc_kernels.hpp"
 
 namespace cpmpc {
 
-template <typename R, typename M>
-__global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename M::Consts k, ExtForce<R> fe_shared, const R* fext,
+// PER_LANE: per-problem dynamics parameters (mpc_kernels.hpp: PlantConsts); the default is the shared set.
+template <typename R, typename M, bool PER_LANE = false>
+__global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg,
+                                                      ExtForce<R> fe_shared, const R* fext,
                                                       int n_sub, R h_last, const R* state, const R* u, R* x_new, R* A_out,
                                                       R* Bu, const R* gbar, R* gx, R* gu) {
   constexpr int NX = M::NX, NQ = M::NQ;
@@ -25,6 +27,7 @@ __global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename M::Cons
   constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B) return;
+  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
   ExtForce<R> fe = fe_shared;
   if (fext) {
     fe.fbx = fext[p];

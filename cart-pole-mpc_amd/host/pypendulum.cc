@@ -226,5 +226,13 @@ PYBIND11_MODULE(pypendulum, m) {
               const Vector2& f_mass) {
              const auto j = self.StepJacobian(params, dt, u, f_base, f_mass);
              return py::make_tuple(std::vector<double>(j.A.begin(), j.A.end()), std::vector<double>(j.B.begin(), j.B.end()));
+           })
+      // (P [4][9] flat row-major, x_new [4]) of the step at the current state, which is not changed (Simulator::StepParamJacobian)
+      .def("step_param_jacobian",
+           [](const Simulator& self, const SingleCartPoleParams& params, double dt, double u, const Vector2& f_base,
+              const Vector2& f_mass) {
+             const auto j = self.StepParamJacobian(params, dt, u, f_base, f_mass);
+             return py::make_tuple(std::vector<double>(j.P.begin(), j.P.end()),
+                                   std::vector<double>(j.x_new.begin(), j.x_new.end()));
            });
 }

@@ -23,7 +23,8 @@ class Simulator {
 
   // The first derivatives of the map Step applies, at the current state (which is not changed): A = dx+/dx row-major
   // [4][4] and B = dx+/du [4], the control held over dt -- the product of the sub-steps' RK4 Jacobians, the wrap of the pole
-  // angle with unit derivative (include/cpmpc.h: cpmpc_sim_step_jac_batch).  Not differentiated: params, the forces, dt.
+  // angle with unit derivative (include/cpmpc.h: cpmpc_sim_step_jac_batch).  Not differentiated here: params
+  // (StepParamJacobian below), the forces, dt.
   // Throws as Step.
   struct StepJacobians {
     std::array<double, 16> A;
@@ -31,6 +32,16 @@ class Simulator {
   };
   [[nodiscard]] StepJacobians StepJacobian(const SingleCartPoleParams& params, double dt, double u, const Vector2& f_base,
                                            const Vector2& f_mass) const;
+
+  // The derivative of the same map in the dynamics parameters, at the current state (which is not changed): P = dx+/dp
+  // row-major [4][9], p in the order of SingleCartPoleParams::ToArray() {m_b, m_1, l_1, g, mu_b, v_mu_b, c_d_1, x_s, k_s},
+  // and the state after the step (include/cpmpc.h: cpmpc_sim_step_param_jac_batch).  Throws as Step.
+  struct StepParamJacobians {
+    std::array<double, 36> P;
+    std::array<double, 4> x_new;
+  };
+  [[nodiscard]] StepParamJacobians StepParamJacobian(const SingleCartPoleParams& params, double dt, double u,
+                                                     const Vector2& f_base, const Vector2& f_mass) const;
 
  private:
   std::array<double, 4> state_{0.0, -3.14159265358979323846 / 2, 0.0, 0.0};  // simulator.hpp:28

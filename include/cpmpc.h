@@ -412,7 +412,8 @@ int cpmpc_sim_step_batch_host(int64_t B, const double* dyn_shared_host, double d
  * whichever others are asked for with it; x_new agrees with cpmpc_sim_step_batch_model's to rounding, not bitwise (the
  * step that also forms the Jacobians is compiled separately).  dt = 0: x_new = state, A = I, Bu = 0, gx = gbar, gu = 0.
  * A problem with a non-finite state has non-finite outputs; no other problem is affected.
- * What is NOT differentiated: the dynamics parameters, the external forces and dt.
+ * What this call does NOT differentiate: the dynamics parameters (cpmpc_sim_step_param_jac_batch below does), the
+ * external forces and dt.
  * Device pointers in `dtype`; asynchronous on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite,
  * a wrong struct_size and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before any device is needed. */
 typedef struct cpmpc_sim_jac {
@@ -436,6 +437,58 @@ int cpmpc_sim_step_jac_batch(int model, int dtype, int64_t B, const double* dyn_
 int cpmpc_sim_step_jac_batch_host(int model, int64_t B, const double* dyn_shared_host, double dt,
                                   const double* state_host, const double* u_host, const double* fext_host,
                                   double* A_host /*nullable*/, double* Bu_host /*nullable*/);
+
+/* ---- per-problem plant parameters, and the plant step's derivative in them ------------------------------------- */
+/* cpmpc_sim_step_batch_model with per-problem dynamics parameters: dyn [NP][B] on the device in `dtype` (NULL: the shared
+ * host set dyn_shared_host, and then the call IS cpmpc_sim_step_batch_model, bitwise -- the same kernel); dyn takes
+ * precedence where both are given, and one of them must be.  A lane's constants are folded from its parameters in the
+ * kernel, in `dtype`, as the solver's per-problem dyn are.  state [NX][B] in/out. */
+int cpmpc_sim_step_dyn_batch(int model, int dtype, int64_t B, const double* dyn_shared_host,
+                             const void* dyn /*[NP][B] device, nullable, takes precedence*/, double dt, const void* u,
+                             const double* fext_host, const void* fext, void* state, void* stream);
+
+/* The plant step of cpmpc_sim_step_jac_batch -- the same sub-steps, from a state that is only READ -- with its derivative in
+ * the DYNAMICS PARAMETERS,
+ *     P = dx+/dp  [NX*NP][B]  (element (r, j) at field r*NP + j),
+ * p = {m_b, m_1, l_1, g, mu_b, v_mu_b, c_d_1, x_s, k_s} (NP = 9) for the 4-state model and {m_b, m_1, m_2, l_1, l_2, g}
+ * (NP = 6) for the 6-state one.  Only first derivatives of the accelerations enter (da/dp beside da/dx): each column of P
+ * is a tangent carried through the RK4 stages of every sub-step, the control and the external forces held, the wrap with
+ * unit derivative.  v_mu_b enters through max(v_mu_b, 1e-6): its column is 0 where the clamp is active; the x_s and k_s
+ * columns are exactly 0 for a problem that stays off the bumpers.  With a cotangent gbar [NX][B] on x+ the call returns
+ * gp = P^T gbar [NP][B] -- P is then never written to memory -- and, for the same cotangent, gx = A^T gbar [NX][B] and
+ * gu = Bu . gbar [B] as cpmpc_sim_step_jac_batch does (they are here because cpmpc_sim_jac has no dyn; with dyn == NULL
+ * they are bitwise that call's).  dyn [NP][B]: per-problem parameters (NULL: dyn_shared_host, which must be given then).
+ * Every output is nullable, only those given are computed, at least one must be given; gp, gx and gu need gbar, and gbar
+ * needs one of them.  No output may overlap state, gbar or dyn.  Each output is bitwise the same whichever others are asked
+ * for with it.  dt = 0: x_new = state, P = 0, gp = 0, gx = gbar, gu = 0.  A problem with a non-finite state or parameter has
+ * non-finite outputs; no other problem is affected.  x_new, P and gp come from one kernel launch (the parameter columns are
+ * computed in compile-time groups, one launch per group, and one group holds them all), gx / gu from the kernel of
+ * cpmpc_sim_step_jac_batch: a call is at most two launches on `stream`, no host synchronisation, no allocation.
+ * What is NOT differentiated: the external forces and dt; and nothing of the CONTROLLER in p (that needs second derivatives
+ * of the dynamics).  dt < 0 or non-finite, a wrong struct_size and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before
+ * any device is needed. */
+typedef struct cpmpc_sim_param_jac {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_param_jac) */
+  const void* state;      /* [NX][B], read only */
+  const void* u;          /* [B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  void* x_new;            /* [NX][B] or NULL */
+  void* P;                /* [NX*NP][B] or NULL */
+  const void* gbar;       /* [NX][B] or NULL */
+  void* gp;               /* [NP][B] or NULL; needs gbar */
+  void* gx;               /* [NX][B] or NULL; needs gbar */
+  void* gu;               /* [B] or NULL; needs gbar */
+} cpmpc_sim_param_jac;
+int cpmpc_sim_step_param_jac_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                                   const cpmpc_sim_param_jac* a, void* stream);
+/* P (and optionally x+) of the same step with HOST doubles and the shared parameter set (fp64 on the GPU; synchronous; used
+ * by the C++ facade, pendulum::Simulator::StepParamJacobian): state_host [NX][B] read only, u_host [B], fext_host shared or
+ * NULL, P_host [NX*NP][B], x_new_host [NX][B] or NULL. */
+int cpmpc_sim_step_param_jac_batch_host(int model, int64_t B, const double* dyn_shared_host, double dt,
+                                        const double* state_host, const double* u_host, const double* fext_host,
+                                        double* P_host, double* x_new_host /*nullable*/);
 
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards

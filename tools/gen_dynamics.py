@@ -29,6 +29,7 @@ Models generated:
 Usage (from the repository root):  python tools/gen_dynamics.py
 Writes   oracle/double_pendulum_gen.inc, oracle/single_pendulum_gen.inc          (C, double)
          cart-pole-mpc_amd/csrc/double_pendulum_gen.hpp, single_pendulum_gen.hpp  (HIP device code, scalar-templated)
+         cart-pole-mpc_amd/csrc/double_pendulum_param_gen.hpp                     (dF/dp, dM/dp of the double pendulum)
 """
 import os
 
@@ -301,6 +302,89 @@ def emit_hip_sc(model, header):
         if e != 0:
             lines.append("  %s = %s;" % (n, pr.doprint(e)))
     lines.append("  (void)x; (void)u; (void)dFdx; (void)dM1; (void)dM2;")
+    lines.append("}")
+    return "\n".join(lines) + "\n"
+
+
+def emit_hip_param(model, header):
+    """The partials of a mass-matrix model's terms with respect to its PARAMETERS, for the plant step's dx+/dp:
+    dFdp[nq x np] row-major and dMdp[np][nq x nq] (dM/dp_j at offset j nq nq), from the raw parameters (an array of the scalar
+    type: per lane or shared), the angles' sines and cosines as inputs like <name>_terms_sc, identically-zero entries as
+    masks (<Name>ParamSparsity; they are never written).  da/dp_j = M^-1 (dF/dp_j - dM/dp_j a) is the solver's, next to this
+    code (csrc/sim_param_kernels.hpp).  Plain arithmetic only, so the header compiles for the host as well."""
+    nq, q, qd, u, M, F, prm = model["nq"], model["q"], model["qd"], model["u"], model["M"], model["F"], model["params"]
+    name = model["name"]
+    cname = "".join(w.capitalize() for w in name.split("_"))
+    x = q + qd
+    npar = len(prm)
+    outs = []
+    for i in range(nq):
+        for j in range(npar):
+            outs.append(("dFdp[%d]" % (i * npar + j), sp.diff(F[i], prm[j])))
+    for j in range(npar):
+        for i in range(nq):
+            for k in range(nq):
+                outs.append(("dMdp[%d]" % (j * nq * nq + i * nq + k), sp.diff(M[i, k], prm[j])))
+    atoms, pre = {}, []
+    for j in model["angles"]:
+        sj, cj = sp.symbols("s%d c%d" % (j, j), real=True)
+        atoms[sp.sin(q[j])] = sj
+        atoms[sp.cos(q[j])] = cj
+    ang = model["angles"]
+    for ia in range(len(ang)):
+        for ib in range(ia + 1, len(ang)):
+            i, j = ang[ia], ang[ib]
+            sd, cd = sp.symbols("sd%d%d cd%d%d" % (i, j, i, j), real=True)
+            si, ci, sj, cj = atoms[sp.sin(q[i])], atoms[sp.cos(q[i])], atoms[sp.sin(q[j])], atoms[sp.cos(q[j])]
+            atoms[sp.sin(q[i] - q[j])] = sd
+            atoms[sp.cos(q[i] - q[j])] = cd
+            atoms[sp.sin(q[j] - q[i])] = -sd
+            atoms[sp.cos(q[j] - q[i])] = cd
+            pre.append((sd, si * cj - ci * sj))
+            pre.append((cd, ci * cj + si * sj))
+    exprs = []
+    for _, e in outs:
+        e = sp.expand(e.subs(atoms))
+        if e.has(sp.sin) or e.has(sp.cos):
+            raise ValueError("trigonometric term outside the atoms: %s" % e)
+        exprs.append(e)
+    repl, red = sp.cse(exprs, symbols=sp.numbered_symbols("t"), optimizations="basic")
+    names = [n for n, _ in outs]
+    pr = _Printer("R")
+    nz = {n: (e != 0) for n, e in zip(names, red)}
+
+    def mask(prefix, count):
+        return "{" + ", ".join("true" if nz["%s[%d]" % (prefix, i)] else "false" for i in range(count)) + "}"
+
+    lines = list(header)
+    lines += ["// which entries are not identically zero (the others are never written: do not read them)",
+              "struct %sParamSparsity {" % cname,
+              "  static constexpr bool dFdp[%d] = %s;" % (nq * npar, mask("dFdp", nq * npar)),
+              "  static constexpr bool dMdp[%d] = %s;" % (npar * nq * nq, mask("dMdp", npar * nq * nq)), "};"]
+    args = ", ".join("const R s%d, const R c%d" % (j, j) for j in model["angles"])
+    lines += ["template <typename R>",
+              "__device__ __forceinline__ void %s_param_terms_sc(const R* p, %s, const R* x, const R u, R* dFdp, R* dMdp) {"
+              % (name, args)]
+    used = set()
+    for _, e in repl:
+        used |= e.free_symbols
+    for e in red:
+        used |= e.free_symbols
+    for i, sym in enumerate(prm):
+        if sym in used:
+            lines.append("  const R %s = p[%d];" % (sym, i))
+    for i, sym in enumerate(x):
+        if sym in used:
+            lines.append("  const R %s = x[%d];" % (sym, i))
+    for sym, e in pre:
+        if sym in used:
+            lines.append("  const R %s = %s;" % (sym, pr.doprint(e)))
+    for sym, e in repl:
+        lines.append("  const R %s = %s;" % (sym, pr.doprint(e)))
+    for n, e in zip(names, red):
+        if e != 0:
+            lines.append("  %s = %s;" % (n, pr.doprint(e)))
+    lines.append("  (void)p; (void)x; (void)u; (void)dFdp; (void)dMdp;")
     lines.append("}")
     return "\n".join(lines) + "\n"
 
@@ -744,6 +828,15 @@ def emit_single_mf(model):
     return "\n".join(text) + "\n"
 
 
+def double_param_file(model):
+    """The text of csrc/double_pendulum_param_gen.hpp for derive_double()'s model."""
+    return (emit_hip_param(model, ["// GENERATED by tools/gen_dynamics.py from the Lagrangian of symbolic/dynamics_double.py:25-107 -- do not edit.",
+                                   "// The partials of M(q) q'' = F(q, q', u) with respect to the parameters p = {m_b, m_1, m_2, l_1, l_2, g}:",
+                                   "// dFdp[3x6] row-major (dF_i/dp_j at i*6 + j), dMdp[6][3x3] (dM_ik/dp_j at j*9 + i*3 + k).",
+                                   "#pragma once", "namespace cpmpc {"])
+            + "}  // namespace cpmpc\n")
+
+
 def main():
     model = derive_double()
     banner = ["// GENERATED by tools/gen_dynamics.py from the Lagrangian of symbolic/dynamics_double.py:25-107 -- do not edit.",
@@ -755,6 +848,7 @@ def main():
            + emit_hip_sc(model, ["// ---- round 6: the same terms with constants folded, trigonometry as inputs and the structure as masks ----"])
            + "}  // namespace cpmpc\n")
     write_if_changed(os.path.join(ROOT, "cart-pole-mpc_amd", "csrc", "double_pendulum_gen.hpp"), hip)
+    write_if_changed(os.path.join(ROOT, "cart-pole-mpc_amd", "csrc", "double_pendulum_param_gen.hpp"), double_param_file(model))
     single = derive_single()
     files = write_single(single)
     print("single pendulum: a0 =", sp.simplify(single["acc"][0]))
