@@ -948,6 +948,135 @@ def sim_step(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.
     return _SimStepFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
 
 
+def _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model):
+    """The inputs the two rollout structs share, checked and set on `a` -> (model id, nx, np, dtype, B, T, host params, keep)."""
+    m, nx, npar = _model_dims(model)
+    dtp = state.dtype
+    _require_cuda_tensor(state, "state", dtp)
+    if state.dim() != 2 or state.shape[0] != nx:
+        raise ValueError("state must be [%d, B]" % nx)
+    B = int(state.shape[1])
+    _require_cuda_tensor(u, "u", dtp)
+    if u.dim() != 2 or int(u.shape[0]) < 1 or int(u.shape[1]) != B:
+        raise ValueError("u must be [T, B] with T >= 1")
+    T = int(u.shape[0])
+    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)   # read by the call itself, before it returns
+    a.x0, a.u = state.data_ptr(), u.data_ptr()
+    a.fext_host = C.cast(shared, C.POINTER(C.c_double))
+    if fext is not None:
+        _require_cuda_tensor(fext, "fext", dtp, (4, B))
+        a.fext = fext.data_ptr()
+    host, dev = _dyn_arg(params, npar, dtp, B)
+    if dev is not None:
+        a.dyn = dev
+    return m, nx, npar, dtp, B, T, host, shared
+
+
+def sim_rollout_states(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single", want=("xs",)):
+    """T ticks of BatchSimulator.step in ONE launch (include/cpmpc.h: cpmpc_sim_rollout_batch): from state [nx, B] (read, not
+    changed) under the controls u [T, B], u[t] held over tick t, a dict with the entries named in `want`,
+        "xs"      [T, nx, B]  xs[t] = the state after tick t, what t + 1 step() calls leave,
+        "x_final" [nx, B]     the state after the last tick.
+    params, dt, f_base / f_mass / fext as BatchSimulator.step's, the same for every tick.  No autograd: sim_rollout has it."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("xs", "x_final") for w in want):
+        raise ValueError("want must name at least one of 'xs', 'x_final'")
+    a = capi.SimRollout(struct_size=C.sizeof(capi.SimRollout))
+    m, nx, npar, dtp, B, T, host, _keep = _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model)
+    shapes = {"xs": (T, nx, B), "x_final": (nx, B)}
+    res = {}
+    for name in want:
+        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
+        setattr(a, name, res[name].data_ptr())
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_rollout_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a), _stream_ptr()))
+    return res
+
+
+def sim_rollout_vjp(params, dt, state, u, xs, gbar=None, gbar_final=None, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0),
+                    model="single", want=("x", "u", "p")):
+    """The reverse mode of sim_rollout_states in ONE launch (include/cpmpc.h: cpmpc_sim_rollout_vjp_batch): cotangents
+    gbar [T, nx, B] on every xs[t] and / or gbar_final [nx, B] on the last state pulled back to the inputs named in `want`
+    -- a dict with
+        "x" [nx, B]  dL/dstate,
+        "u" [T, B]   dL/du,
+        "p" [np, B]  dL/dparams (per problem, also where params is one shared set: sum over the batch for its gradient).
+    xs [T, nx, B] is a sim_rollout_states call's at the same inputs (its last row is not read; None is allowed for T = 1).
+    Reverse over the ticks, forward inside a tick; the tick's A, Bu and P are contracted in registers and nothing per tick
+    goes to memory.  Not differentiated: the external forces and dt.  Other arguments as sim_rollout_states'."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("x", "u", "p") for w in want):
+        raise ValueError("want must name at least one of 'x', 'u', 'p'")
+    if gbar is None and gbar_final is None:
+        raise ValueError("one of gbar, gbar_final must be given")
+    a = capi.SimRolloutVjp(struct_size=C.sizeof(capi.SimRolloutVjp))
+    m, nx, npar, dtp, B, T, host, _keep = _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model)
+    if xs is not None:
+        _require_cuda_tensor(xs, "xs", dtp, (T, nx, B))
+        a.xs = xs.data_ptr()
+    elif T > 1:
+        raise ValueError("xs (a sim_rollout_states call's) is required when T > 1")
+    if gbar is not None:
+        _require_cuda_tensor(gbar, "gbar", dtp, (T, nx, B))
+        a.gbar = gbar.data_ptr()
+    if gbar_final is not None:
+        _require_cuda_tensor(gbar_final, "gbar_final", dtp, (nx, B))
+        a.gbar_final = gbar_final.data_ptr()
+    fields = {"x": ("g_x0", (nx, B)), "u": ("g_u", (T, B)), "p": ("g_p", (npar, B))}
+    res = {}
+    for w in want:
+        res[w] = torch.empty(fields[w][1], dtype=dtp, device=state.device)
+        setattr(a, fields[w][0], res[w].data_ptr())
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_rollout_vjp_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                           _stream_ptr()))
+    return res
+
+
+class _SimRolloutFunction(torch.autograd.Function):
+    """T plant ticks as a function of (state, u) and, where params is a tensor, of the parameters: forward is one
+    sim_rollout_states launch, backward one sim_rollout_vjp launch at the saved inputs and checkpoints (sim_rollout)."""
+
+    @staticmethod
+    def forward(ctx, state, u, params, dt, fext, f_base, f_mass, model):
+        per_problem = isinstance(params, torch.Tensor)
+        ctx.args = (params.detach().clone() if per_problem else [float(v) for v in params], float(dt),
+                    None if fext is None else fext.detach().clone(), tuple(f_base), tuple(f_mass), model)
+        x0, uu = state.detach().clone(), u.detach().clone()
+        xs = sim_rollout_states(ctx.args[0], dt, x0, uu, fext=fext, f_base=f_base, f_mass=f_mass, model=model)["xs"]
+        ctx.save_for_backward(x0, uu, xs)
+        return xs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gbar):
+        state, u, xs = ctx.saved_tensors
+        params, dt, fext, f_base, f_mass, model = ctx.args
+        want = [name for name, i in (("x", 0), ("u", 1)) if ctx.needs_input_grad[i]]
+        if isinstance(params, torch.Tensor) and ctx.needs_input_grad[2]:
+            want.append("p")
+        res = {}
+        if want:
+            res = sim_rollout_vjp(params, dt, state, u, xs, gbar=gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass,
+                                  model=model, want=want)
+        return res.get("x"), res.get("u"), res.get("p"), None, None, None, None, None
+
+
+def sim_rollout(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
+    """T ticks of BatchSimulator.step as ONE differentiable function: returns xs [T, nx, B], xs[t] the state after tick t
+    under the controls u [T, B] (sim_rollout_states; `state` is not changed), attached to the autograd graph of state and u.
+    Forward is one launch; backward is one sim_rollout_vjp launch on the current stream at the forward's own copies of
+    (state, u) and its xs, and is differentiable once only.  A loss on the last state alone reads xs[-1].  The wrap of the
+    pole angles has unit derivative.
+
+    params: np floats -- gradients flow to state and u alone -- or an [np, B] tensor of per-problem parameters.  When that
+    tensor requires grad, the same backward launch returns dL/dp [np, B] for it beside the gradients for state and u.  A
+    SHARED parameter set that should receive a gradient is passed as p.expand(np, B).contiguous() of an [np, 1] tensor p by
+    the caller: autograd then sums the per-problem gradients over the batch.  The external forces and dt are not
+    differentiated."""
+    return _SimRolloutFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
+
+
 class BatchSimulator:
     """B independent pendulum::Simulator plants (optimization/simulator.hpp:10-29)."""
 
@@ -988,6 +1117,23 @@ class BatchSimulator:
         are not differentiated."""
         self.state = sim_step(params, dt, self.state, u, fext=fext, f_base=f_base, f_mass=f_mass, model=self.model)
         return self.state
+
+    def rollout(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
+        """T step() calls in one launch (sim_rollout_states): u [T, B], u[t] held over tick t.  The state becomes the one
+        after the last tick; returns xs [T, nx, B], the state after every tick."""
+        res = sim_rollout_states(params.detach() if isinstance(params, torch.Tensor) else params, dt, self.state, u, fext=fext,
+                                 f_base=f_base, f_mass=f_mass, model=self.model, want=("xs", "x_final"))
+        self.state = res["x_final"]
+        return res["xs"]
+
+    def rollout_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
+        """rollout() with a backward: xs = sim_rollout(params, dt, self.state, u, ...) is returned, attached to the autograd
+        graph of the state before the rollout, of u and -- where it is an [np, B] tensor requiring grad -- of params;
+        self.state becomes a copy of xs[-1], attached likewise (a copy: step() works in place, and xs is what the backward
+        reads).  The external forces and dt are not differentiated."""
+        xs = sim_rollout(params, dt, self.state, u, fext=fext, f_base=f_base, f_mass=f_mass, model=self.model)
+        self.state = xs[-1].clone()
+        return xs
 
 
 class ClosedLoop:

@@ -50,6 +50,7 @@ SYMBOLS = [
     "cpmpc_plan_weight_vjp_batch", "cpmpc_plan_weight_vjp_batch_host",
     "cpmpc_sim_step_jac_batch", "cpmpc_sim_step_jac_batch_host",
     "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
+    "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch",
 ]
 
 
@@ -253,6 +254,40 @@ class SimParamJac(C.Structure):
     ]
 
 
+class SimRollout(C.Structure):
+    """cpmpc_sim_rollout: device pointers of cpmpc_sim_rollout_batch; x0, u [T][B] and dyn are read, xs and x_final are
+    nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("xs", C.c_void_p),
+        ("x_final", C.c_void_p),
+    ]
+
+
+class SimRolloutVjp(C.Structure):
+    """cpmpc_sim_rollout_vjp: device pointers of cpmpc_sim_rollout_vjp_batch; x0, u, dyn, xs (a forward call's) and the
+    cotangents gbar / gbar_final are read, g_x0, g_u and g_p are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("xs", C.c_void_p),
+        ("gbar", C.c_void_p),
+        ("gbar_final", C.c_void_p),
+        ("g_x0", C.c_void_p),
+        ("g_u", C.c_void_p),
+        ("g_p", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -383,6 +418,8 @@ def load():
     L.cpmpc_sim_step_dyn_batch.argtypes = [i32, i32, i64, _dp, vp, dbl, vp, _dp, vp, vp, vp]
     L.cpmpc_sim_step_param_jac_batch.argtypes = [i32, i32, i64, _dp, dbl, C.POINTER(SimParamJac), vp]
     L.cpmpc_sim_step_param_jac_batch_host.argtypes = [i32, i64, _dp, dbl, _dp, _dp, _dp, _dp, _dp]
+    L.cpmpc_sim_rollout_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRollout), vp]
+    L.cpmpc_sim_rollout_vjp_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutVjp), vp]
     _lib = L
     return L
 

@@ -941,6 +941,105 @@ extern "C" int cpmpc_sim_step_param_jac_batch(int model, int dtype, int64_t B, c
   return CPMPC_OK;
 }
 
+// ---- the plant over T ticks and its adjoint (sim_rollout_kernels.hpp) ------------------------------------------------
+// What the two rollout calls check alike (no device needed); `what` names the struct
+static int check_rollout_common(const char* what, uint64_t struct_size, size_t size_here, const void* x0, const void* u,
+                                const double* dyn_shared_host, const void* dyn, double dt, int T, int model, int dtype,
+                                int64_t B) {
+  if (struct_size != size_here)
+    return fail(CPMPC_ERR_INVALID_ARG, "%s.struct_size is %llu, this library's is %zu (set it to sizeof(%s))", what,
+                (unsigned long long)struct_size, size_here, what);
+  if (!x0 || !u) return fail(CPMPC_ERR_INVALID_ARG, "null argument (x0, u)");
+  if (!dyn_shared_host && !dyn) return fail(CPMPC_ERR_INVALID_ARG, "null argument (neither dyn_shared_host nor dyn is given)");
+  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  if (T < 1) return fail(CPMPC_ERR_INVALID_ARG, "T must be >= 1");
+  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
+  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
+  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
+  return CPMPC_OK;
+}
+
+struct RolloutSpan {
+  const void* p;
+  size_t rows;  // of B numbers each
+  const char* name;
+};
+// lanes run in any order: an output that overlaps what another lane has yet to read is refused
+static int check_rollout_overlap(const RolloutSpan* outs, int n_out, const RolloutSpan* ins, int n_in, size_t row) {
+  for (int o = 0; o < n_out; ++o)
+    for (int i = 0; i < n_in; ++i) {
+      if (!outs[o].p || !ins[i].p) continue;
+      const char *o0 = (const char*)outs[o].p, *i0 = (const char*)ins[i].p;
+      if (o0 < i0 + ins[i].rows * row && i0 < o0 + outs[o].rows * row)
+        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", outs[o].name,
+                    ins[i].name);
+    }
+  return CPMPC_OK;
+}
+
+static int check_sim_rollout_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                  const cpmpc_sim_rollout* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout)");
+  int rc = check_rollout_common("cpmpc_sim_rollout", a->struct_size, sizeof(cpmpc_sim_rollout), a->x0, a->u, dyn_shared_host,
+                                a->dyn, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->xs && !a->x_final) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model), nt = (size_t)T;
+  const size_t np = (size_t)cpmpc_model_num_params(model);
+  const RolloutSpan outs[2] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}};
+  const RolloutSpan ins[4] = {{a->x0, nx, "x0"}, {a->u, nt, "u"}, {a->fext, 4, "fext"}, {a->dyn, np, "dyn"}};
+  return check_rollout_overlap(outs, 2, ins, 4, row);
+}
+
+extern "C" int cpmpc_sim_rollout_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                       const cpmpc_sim_rollout* a, void* stream) {
+  int rc = check_sim_rollout_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  rc = current_device_ok();
+  if (rc) return rc;
+  int n_sub = 0;
+  double h_last = 0.0;
+  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  if (rc) return rc;
+  engine_for(dtype, model)->sim_rollout(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
+}
+
+static int check_sim_rollout_vjp_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                      const cpmpc_sim_rollout_vjp* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout_vjp)");
+  int rc = check_rollout_common("cpmpc_sim_rollout_vjp", a->struct_size, sizeof(cpmpc_sim_rollout_vjp), a->x0, a->u,
+                                dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->g_x0 && !a->g_u && !a->g_p) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (!a->gbar && !a->gbar_final) return fail(CPMPC_ERR_INVALID_ARG, "neither gbar nor gbar_final is given");
+  if (T > 1 && !a->xs) return fail(CPMPC_ERR_INVALID_ARG, "xs (a forward call's checkpoints) is required when T > 1");
+  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model), nt = (size_t)T;
+  const size_t np = (size_t)cpmpc_model_num_params(model);
+  const RolloutSpan outs[3] = {{a->g_x0, nx, "g_x0"}, {a->g_u, nt, "g_u"}, {a->g_p, np, "g_p"}};
+  const RolloutSpan ins[7] = {{a->x0, nx, "x0"},           {a->u, nt, "u"},
+                              {a->fext, 4, "fext"},        {a->dyn, np, "dyn"},
+                              {a->xs, nt * nx, "xs"},      {a->gbar, nt * nx, "gbar"},
+                              {a->gbar_final, nx, "gbar_final"}};
+  return check_rollout_overlap(outs, 3, ins, 7, row);
+}
+
+extern "C" int cpmpc_sim_rollout_vjp_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                           const cpmpc_sim_rollout_vjp* a, void* stream) {
+  int rc = check_sim_rollout_vjp_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  rc = current_device_ok();
+  if (rc) return rc;
+  int n_sub = 0;
+  double h_last = 0.0;
+  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  if (rc) return rc;
+  engine_for(dtype, model)->sim_rollout_vjp(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CPMPC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

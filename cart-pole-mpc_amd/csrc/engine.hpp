@@ -236,6 +236,13 @@ struct Engine {
   // not null
   void (*sim_param_jac)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_param_jac* a,
                         hipStream_t stream);
+  // T ticks of the plant step in one launch, xs [T][NX][B] and / or x_final [NX][B] (sim_rollout_kernels.hpp), with shared
+  // or per-problem parameters.  n_sub = 0 copies x0
+  void (*sim_rollout)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_rollout* a,
+                      hipStream_t stream);
+  // the adjoint of that rollout in one launch: g_x0, g_u [T][B], g_p of `a` that are not null (sim_rollout_vjp_kernel)
+  void (*sim_rollout_vjp)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                          const cpmpc_sim_rollout_vjp* a, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -15,6 +15,7 @@
 #include "plan_weight_vjp_kernels.hpp"
 #include "sim_jac_kernels.hpp"
 #include "sim_param_kernels.hpp"
+#include "sim_rollout_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -577,6 +578,40 @@ static void sim_param_jac_impl(int64_t B, const double* dyn_shared_host, int n_s
   }
 }
 
+// ---- the plant over T ticks and its adjoint, one launch each (sim_rollout_kernels.hpp) ----------------------------------
+template <typename R, typename M>
+static void sim_rollout_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                             const cpmpc_sim_rollout* a, hipStream_t stream) {
+  if (a->dyn)
+    hipLaunchKernelGGL((sim_rollout_kernel<R, M, true>), grid_for(B), dim3(64), 0, stream, B, (const R*)a->dyn,
+                       ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, T, (const R*)a->x0,
+                       (const R*)a->u, (R*)a->xs, (R*)a->x_final);
+  else
+    hipLaunchKernelGGL((sim_rollout_kernel<R, M, false>), grid_for(B), dim3(64), 0, stream, B,
+                       M::template make<double>(dyn_shared_host), ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub,
+                       (R)h_last, T, (const R*)a->x0, (const R*)a->u, (R*)a->xs, (R*)a->x_final);
+}
+
+template <typename R, typename M, bool PER_LANE>
+static void launch_rollout_vjp(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                               const cpmpc_sim_rollout_vjp* a, hipStream_t stream) {
+  typename M::Consts k{};
+  RawParams<R, M::NP> raw{};
+  if constexpr (!PER_LANE) {
+    k = M::template make<double>(dyn_shared_host);
+    for (int i = 0; i < M::NP; ++i) raw.p[i] = (R)dyn_shared_host[i];
+  }
+  hipLaunchKernelGGL((sim_rollout_vjp_kernel<R, M, PER_LANE>), grid_for(B), dim3(64), 0, stream, B, k, raw, (const R*)a->dyn,
+                     ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u,
+                     (const R*)a->xs, (const R*)a->gbar, (const R*)a->gbar_final, (R*)a->g_x0, (R*)a->g_u, (R*)a->g_p);
+}
+template <typename R, typename M>
+static void sim_rollout_vjp_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                                 const cpmpc_sim_rollout_vjp* a, hipStream_t stream) {
+  if (a->dyn) launch_rollout_vjp<R, M, true>(B, dyn_shared_host, n_sub, h_last, T, a, stream);
+  else launch_rollout_vjp<R, M, false>(B, dyn_shared_host, n_sub, h_last, T, a, stream);
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
 // linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
@@ -713,6 +748,6 @@ static int debug_read_impl(int which, unsigned long long* out) {
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
                              &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>, &sim_dyn_impl<R, M>,           \
-                             &sim_param_jac_impl<R, M>};                                                             \
+                             &sim_param_jac_impl<R, M>,   &sim_rollout_impl<R, M>,     &sim_rollout_vjp_impl<R, M>};  \
     return &e;                                                                                                       \
   }

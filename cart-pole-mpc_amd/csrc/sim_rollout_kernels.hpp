@@ -1,0 +1,220 @@
+// sim_rollout_kernels.hpp -- the plant over T ticks in one kernel, and its adjoint in one kernel:
+//     x_{t+1} = Step(x_t, u_t, dt),  t = 0 .. T-1,
+// Step being Simulator::Step (simulator.cc:11-36) exactly as sim_kernel runs it -- n_sub sub-steps of 1 ms, the last one
+// h_last, the control held over the tick, the pole angles wrapped after each sub-step.  dt, the external forces and the
+// dynamics parameters are those of every tick.  One problem per lane, no LDS; the tick loop stays on the device.
+//
+// sim_rollout_kernel: the tick body is sim_kernel's loop; after tick t it stores x_{t+1} to xs [T][NX][B] (field t*NX + r)
+// and after the last one to x_final [NX][B], each where its pointer is given (a wave-uniform choice).
+//
+// sim_rollout_vjp_kernel: REVERSE over the ticks, FORWARD inside a tick.  With the cotangents gbar [T][NX][B] on every
+// x_{t+1} and / or gbar_final [NX][B] on x_T,
+//     lambda = 0, gp = 0
+//     for t = T-1 .. 0:
+//         lambda += gbar[t]  (+= gbar_final at t = T-1)
+//         x_t = (t == 0) ? x0 : xs[t-1]                       -- a forward call's checkpoints; row T-1 is never loaded
+//         pass B: sim_param_jac_kernel's sub-step loop from x_t, every column -> gp += P^T lambda   (where g_p is given)
+//         pass A: sim_jac_kernel's sub-step loop from x_t      -> g_u[t] = gamma . lambda,  lambda <- Phi^T lambda
+//     g_x0 = lambda, g_p = gp
+// lambda and gp stay in registers across the ticks.  The passes run one after the other (B before A, so that one copy of
+// lambda serves both), so what is live at once is the larger of the two existing kernels' sets plus lambda and gp.
+// Nothing per sub-step is stored; the adjoint of RK4 inside a tick is not built.  n_sub == 0 is the identity
+// map: g_x0 is the cotangents added up in that order, g_u and g_p are zeros.  Not differentiated: the external forces and
+// dt; the wrap has unit derivative.
+#pragma once
+#include "sim_param_kernels.hpp"
+
+namespace cpmpc {
+
+template <typename R, typename M, bool PER_LANE>
+__global__ __launch_bounds__(64) void sim_rollout_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg,
+                                                          ExtForce<R> fe_shared, const R* fext, int n_sub, R h_last, int T,
+                                                          const R* x0, const R* u, R* xs_out, R* x_final) {
+  constexpr int NX = M::NX;
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= B) return;
+  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
+  ExtForce<R> fe = fe_shared;
+  if (fext) {
+    fe.fbx = fext[p];
+    fe.fmx = fext[2 * B + p];
+    fe.fmy = fext[3 * B + p];
+  }
+  R xs[NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
+  const R internal_dt = R(0.001);
+#pragma unroll 1
+  for (int t = 0; t < T; ++t) {
+    const R uu = u[(int64_t)t * B + p];
+    typename M::StepCache chain;
+#pragma unroll 1
+    for (int i = 0; i < n_sub; ++i) {
+      const R h = (i + 1 == n_sub) ? h_last : internal_dt;
+      if (i % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
+      rk4_step_m<R, M, true>(k, h, xs, uu, fe, chain);
+      wrap_angles<R, M>(xs);
+    }
+    if (xs_out)
+#pragma unroll
+      for (int r = 0; r < NX; ++r) xs_out[((int64_t)t * NX + r) * B + p] = xs[r];
+  }
+  if (x_final)
+#pragma unroll
+    for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
+}
+
+// PER_LANE: the parameters are dyn [NP][B], read per lane, and the constants are M::make<R> of them in the kernel, as
+// sim_param_jac_kernel does; else `k_shared` and `raw` are the shared set's.
+template <typename R, typename M, bool PER_LANE>
+__global__ __launch_bounds__(64) void sim_rollout_vjp_kernel(int64_t B, typename M::Consts k_shared, RawParams<R, M::NP> raw,
+                                                              const R* dyn, ExtForce<R> fe_shared, const R* fext, int n_sub,
+                                                              R h_last, int T, const R* x0, const R* u, const R* xs_in,
+                                                              const R* gbar, const R* gbar_final, R* g_x0, R* g_u, R* g_p) {
+  constexpr int NX = M::NX, NQ = M::NQ, NP = M::NP;
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);  // sim_jac_kernel's closed-form columns
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= B) return;
+  ExtForce<R> fe = fe_shared;
+  if (fext) {
+    fe.fbx = fext[p];
+    fe.fmx = fext[2 * B + p];
+    fe.fmy = fext[3 * B + p];
+  }
+  typename M::Consts k = k_shared;
+  if constexpr (PER_LANE) {
+    R prm[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) prm[i] = dyn[i * B + p];
+    k = M::template make<R>(prm);
+  }
+
+  R lam[NX], gp[NP];
+#pragma unroll
+  for (int r = 0; r < NX; ++r) lam[r] = R(0);
+#pragma unroll
+  for (int j = 0; j < NP; ++j) gp[j] = R(0);
+
+  const R internal_dt = R(0.001);
+#pragma unroll 1
+  for (int t = T - 1; t >= 0; --t) {
+    if (gbar)
+#pragma unroll
+      for (int r = 0; r < NX; ++r) lam[r] += gbar[((int64_t)t * NX + r) * B + p];
+    if (gbar_final && t == T - 1)
+#pragma unroll
+      for (int r = 0; r < NX; ++r) lam[r] += gbar_final[r * B + p];
+    if (n_sub == 0) {  // the identity map: the cotangent itself, not its products with ones and zeros
+      if (g_u) g_u[(int64_t)t * B + p] = R(0);
+      continue;
+    }
+    const R* xt = (t == 0) ? x0 : xs_in + (int64_t)(t - 1) * NX * B;
+    const R uu = u[(int64_t)t * B + p];
+
+    // ---- pass B: the parameter tangents of the tick, sim_param_jac_kernel's loop over every column.  It runs FIRST: it
+    // needs the lambda pass A replaces, and so no second copy of lambda is live beside the tangents ---------------------
+    if (g_p) {
+      R prm[NP];  // the raw parameters, read here every tick rather than held across pass A
+      if constexpr (PER_LANE) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) prm[i] = dyn[i * B + p];
+      } else {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) prm[i] = raw.p[i];
+      }
+      R xs[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) xs[r] = xt[r * B + p];
+      R Tn[NP][NX];
+#pragma unroll
+      for (int j = 0; j < NP; ++j)
+#pragma unroll
+        for (int r = 0; r < NX; ++r) Tn[j][r] = R(0);
+      typename M::StepCache chain;
+#pragma unroll 1
+      for (int i = 0; i < n_sub; ++i) {
+        const R h = (i + 1 == n_sub) ? h_last : internal_dt;
+        rk4_step_param_m<R, M, true, 0, NP>(k, prm, h, xs, uu, fe, Tn, chain);
+        wrap_angles<R, M>(xs);
+      }
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        R acc = Tn[j][0] * lam[0];
+#pragma unroll
+        for (int r = 1; r < NX; ++r) acc += Tn[j][r] * lam[r];
+        gp[j] += acc;
+      }
+    }
+    // ---- pass A: Phi and gamma of the tick, sim_jac_kernel's loop; lambda <- Phi^T lambda ------------------------------
+    {
+      R lam_new[NX];
+      R xs[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) xs[r] = xt[r * B + p];
+      R Phi[NX][NX], gam[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) {
+#pragma unroll
+        for (int c = 0; c < NX; ++c)
+          if (!((TRIV >> c) & 1u)) Phi[r][c] = (r == c) ? R(1) : R(0);
+        gam[r] = R(0);
+      }
+      R t_sum = R(0);
+      typename M::StepCache chain;
+#pragma unroll 1
+      for (int i = 0; i < n_sub; ++i) {
+        const R h = (i + 1 == n_sub) ? h_last : internal_dt;
+        R A[NX][NX], Bv[NX];
+        rk4_step_jac_m<R, M, true>(k, h, xs, uu, fe, A, Bv, chain);
+        wrap_angles<R, M>(xs);
+#pragma unroll
+        for (int c = 0; c < NX; ++c) {
+          if ((TRIV >> c) & 1u) continue;
+          R v[NX], y[NX];
+#pragma unroll
+          for (int m = 0; m < NX; ++m) v[m] = Phi[m][c];
+          step_jac_apply<R, M>(A, h, v, y);
+#pragma unroll
+          for (int r = 0; r < NX; ++r) Phi[r][c] = y[r];
+        }
+        {
+          R y[NX];
+          step_jac_apply<R, M>(A, h, gam, y);
+#pragma unroll
+          for (int r = 0; r < NX; ++r) gam[r] = y[r] + Bv[r];
+        }
+        if (TRIV != 0u) t_sum += h;
+      }
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        R acc;
+        if ((TRIV >> c) & 1u) {
+          acc = lam[c];
+          if (c >= NQ) acc += t_sum * lam[c - NQ];
+        } else {
+          acc = Phi[0][c] * lam[0];
+#pragma unroll
+          for (int r = 1; r < NX; ++r) acc += Phi[r][c] * lam[r];
+        }
+        lam_new[c] = acc;
+      }
+      if (g_u) {
+        R acc = gam[0] * lam[0];
+#pragma unroll
+        for (int r = 1; r < NX; ++r) acc += gam[r] * lam[r];
+        g_u[(int64_t)t * B + p] = acc;
+      }
+#pragma unroll
+      for (int r = 0; r < NX; ++r) lam[r] = lam_new[r];
+    }
+  }
+
+  if (g_x0)
+#pragma unroll
+    for (int r = 0; r < NX; ++r) g_x0[r * B + p] = lam[r];
+  if (g_p)
+#pragma unroll
+    for (int j = 0; j < NP; ++j) g_p[j * B + p] = gp[j];
+}
+
+}  // namespace cpmpc

@@ -490,6 +490,61 @@ int cpmpc_sim_step_param_jac_batch_host(int model, int64_t B, const double* dyn_
                                         const double* state_host, const double* u_host, const double* fext_host,
                                         double* P_host, double* x_new_host /*nullable*/);
 
+/* ---- the plant over T ticks in one launch, and its adjoint in one launch ---------------------------------------- */
+/* x_{t+1} = Step(x_t, u_t, dt) for t = 0 .. T-1, Step being cpmpc_sim_step_dyn_batch's -- the same sub-steps, the control
+ * u [T][B] held over its tick, the pole angles wrapped after each sub-step; dt, the external forces and the parameters
+ * (dyn [NP][B], or dyn_shared_host where dyn is NULL; one of them must be given) are those of every tick.  x0 is only
+ * READ.  xs [T][NX][B] receives x_{t+1} at field t*NX + r, x_final [NX][B] receives x_T; each is nullable, at least one must
+ * be given, and each is bitwise the same whether or not the other is asked for.  A tick runs the plant step's own code:
+ * xs[t] is what t + 1 cpmpc_sim_step_dyn_batch calls leave.  dt = 0: every xs[t] and x_final are x0.  No output may overlap
+ * x0, u, fext or dyn.  A problem with non-finite data has non-finite outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_rollout {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_rollout) */
+  const void* x0;         /* [NX][B], read only */
+  const void* u;          /* [T][B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  void* xs;               /* [T][NX][B] or NULL */
+  void* x_final;          /* [NX][B] or NULL */
+} cpmpc_sim_rollout;
+int cpmpc_sim_rollout_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                            const cpmpc_sim_rollout* a, void* stream);
+
+/* The adjoint of that rollout: cotangents gbar [T][NX][B] on every x_{t+1} and / or gbar_final [NX][B] on x_T (at least one
+ * must be given) pulled back to x0, to the T controls and to the parameters,
+ *     g_x0 [NX][B],   g_u [T][B],   g_p [NP][B]
+ * (g_p per problem, also where the parameters are the shared set: sum over the batch for its gradient).  Reverse over the
+ * ticks, forward inside a tick: from the last tick down to the first the kernel adds the tick's cotangent to lambda, takes
+ * x_t from x0 (t = 0) or from row t-1 of xs -- a cpmpc_sim_rollout_batch call's, required when T > 1; row T-1 is never read
+ * -- forms the tick's A and Bu as cpmpc_sim_step_jac_batch does and its P as cpmpc_sim_step_param_jac_batch does, and
+ * contracts them with lambda in registers: g_u[t] = Bu . lambda, g_p += P^T lambda, lambda <- A^T lambda.  Nothing per
+ * sub-step or per tick is stored.  Every output is nullable, only those given are computed, at least one must be given, and
+ * each is bitwise the same whichever others are asked for.  dt = 0: g_x0 is the cotangents added up (gbar[T-1], gbar_final,
+ * gbar[T-2], ...), g_u = 0, g_p = 0.  No output may overlap x0, u, fext, dyn, xs, gbar or gbar_final.
+ * What is NOT differentiated: the external forces and dt; the wrap of the pole angles has unit derivative.  A problem with
+ * non-finite data has non-finite outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_rollout_vjp {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_rollout_vjp) */
+  const void* x0;         /* [NX][B], read only */
+  const void* u;          /* [T][B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* xs;         /* [T][NX][B]: a forward call's; required when T > 1 */
+  const void* gbar;       /* [T][NX][B] or NULL */
+  const void* gbar_final; /* [NX][B] or NULL */
+  void* g_x0;             /* [NX][B] or NULL */
+  void* g_u;              /* [T][B] or NULL */
+  void* g_p;              /* [NP][B] or NULL */
+} cpmpc_sim_rollout_vjp;
+int cpmpc_sim_rollout_vjp_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                const cpmpc_sim_rollout_vjp* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
