@@ -726,11 +726,16 @@ int current_device_ok() {
   return check_device(dev);
 }
 
-static int check_piece_args(int model, int dtype, int64_t B) {
+static int check_model_dtype_batch(int model, int dtype, int64_t B) {
   if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
   if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
   if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
-  return current_device_ok();
+  return CPMPC_OK;
+}
+
+static int check_piece_args(int model, int dtype, int64_t B) {
+  int rc = check_model_dtype_batch(model, dtype, B);
+  return rc ? rc : current_device_ok();
 }
 
 extern "C" int cpmpc_dynamics_batch_model(int model, int dtype, int64_t B, const double* dyn_shared_host,
@@ -779,8 +784,12 @@ extern "C" int cpmpc_linearize_batch(cpmpc_solver* s, int64_t B, const double* d
   return CPMPC_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the plant calls: one step, the step with its derivatives, the rollout and its adjoint.  Each has its own argument rules;
+// what they check alike and how they end is below.
+// ------------------------------------------------------------------------------------------------
 // simulator.cc:18-22 evaluated in double: the number of sub-steps of a plant step of length dt and the size of the last one
-// (n_sub = 0 for dt = 0).  Shared by the plant step and the plant step with derivatives, so both take the same sub-steps.
+// (n_sub = 0 for dt = 0).  Shared by every plant call, so all take the same sub-steps.
 static int sim_sub_steps(double dt, int* n_sub_out, double* h_last_out) {
   const double internal_dt = 0.001;
   int n_sub = 0;
@@ -797,21 +806,67 @@ static int sim_sub_steps(double dt, int* n_sub_out, double* h_last_out) {
   return CPMPC_OK;
 }
 
-extern "C" int cpmpc_sim_step_batch_model(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
-                                          const void* u, const double* fext_host, const void* fext, void* state,
-                                          void* stream) {
-  if (!dyn_shared_host || !u || !state) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+// The checks every plant call makes (no device needed).  Two functions, not one, because the calls with an argument struct
+// test their own rules between the two, and the order of the tests is part of what a caller sees.
+static int check_plant_dt(double dt) {
   if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
-  int rc = check_piece_args(model, dtype, B);
+  return CPMPC_OK;
+}
+// ... and check_model_dtype_batch above.  `what` names the argument struct:
+static int check_struct_size(const char* what, uint64_t struct_size, size_t size_here) {
+  if (struct_size != size_here)
+    return fail(CPMPC_ERR_INVALID_ARG, "%s.struct_size is %llu, this library's is %zu (set it to sizeof(%s))", what,
+                (unsigned long long)struct_size, size_here, what);
+  return CPMPC_OK;
+}
+
+struct ArraySpan {
+  const void* p;  // NULL: not given, overlaps nothing
+  size_t rows;    // of B numbers each
+  const char* name;
+};
+// Lanes run in any order, and a lane reads its inputs before it writes but another lane's may not have been read yet: an
+// output that overlaps an array the call only reads is refused.  `row` is the size of B numbers in bytes.
+template <int N_OUT, int N_IN>
+static int check_no_overlap(const ArraySpan (&outs)[N_OUT], const ArraySpan (&ins)[N_IN], size_t row) {
+  for (const ArraySpan& o : outs)
+    for (const ArraySpan& in : ins) {
+      if (!o.p || !in.p) continue;
+      const char *o0 = (const char*)o.p, *i0 = (const char*)in.p;
+      if (o0 < i0 + in.rows * row && i0 < o0 + o.rows * row)
+        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", o.name, in.name);
+    }
+  return CPMPC_OK;
+}
+static size_t row_bytes(int dtype, int64_t B) { return (size_t)B * (dtype == CPMPC_F64 ? 8 : 4); }
+
+// How every plant call ends once its arguments are accepted: the device, the sub-steps of dt, the engine call as
+// launch(n_sub, h_last).  skip_empty: the call has nothing to write for dt = 0 and launches nothing then.
+template <typename Launch>
+static int run_plant_call(double dt, bool skip_empty, Launch launch) {
+  int rc = current_device_ok();
   if (rc) return rc;
   int n_sub = 0;
   double h_last = 0.0;
   rc = sim_sub_steps(dt, &n_sub, &h_last);
   if (rc) return rc;
-  if (n_sub == 0) return CPMPC_OK;
-  engine_for(dtype, model)->sim(B, dyn_shared_host, fext_host, fext, n_sub, h_last, u, state, (hipStream_t)stream);
+  if (skip_empty && n_sub == 0) return CPMPC_OK;
+  launch(n_sub, h_last);
   HIP_TRY(hipGetLastError());
   return CPMPC_OK;
+}
+
+extern "C" int cpmpc_sim_step_batch_model(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                                          const void* u, const double* fext_host, const void* fext, void* state,
+                                          void* stream) {
+  if (!dyn_shared_host || !u || !state) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
+  int rc = check_plant_dt(dt);
+  if (rc) return rc;
+  rc = check_model_dtype_batch(model, dtype, B);
+  if (rc) return rc;
+  return run_plant_call(dt, true, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim(B, dyn_shared_host, fext_host, fext, n_sub, h_last, u, state, (hipStream_t)stream);
+  });
 }
 extern "C" int cpmpc_sim_step_batch(int dtype, int64_t B, const double* dyn_shared_host, double dt, const void* u,
                                     const double* fext_host, const void* fext, void* state, void* stream) {
@@ -822,30 +877,20 @@ extern "C" int cpmpc_sim_step_batch(int dtype, int64_t B, const double* dyn_shar
 // The argument checks of cpmpc_sim_step_jac_batch (no device needed)
 static int check_sim_jac_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, const cpmpc_sim_jac* a) {
   if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_jac)");
-  if (a->struct_size != sizeof(cpmpc_sim_jac))
-    return fail(CPMPC_ERR_INVALID_ARG, "cpmpc_sim_jac.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_sim_jac))",
-                (unsigned long long)a->struct_size, sizeof(cpmpc_sim_jac));
+  int rc = check_struct_size("cpmpc_sim_jac", a->struct_size, sizeof(cpmpc_sim_jac));
+  if (rc) return rc;
   if (!dyn_shared_host || !a->state || !a->u) return fail(CPMPC_ERR_INVALID_ARG, "null argument (dyn, state, u)");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  rc = check_plant_dt(dt);
+  if (rc) return rc;
   if ((a->gx || a->gu) && !a->gbar) return fail(CPMPC_ERR_INVALID_ARG, "gx / gu are given without gbar");
   if (a->gbar && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "gbar is given with neither gx nor gu");
   if (!a->x_new && !a->A && !a->Bu && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
-  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
-  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
-  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
-  // the kernel reads a lane's state and cotangent once, before it writes, but another lane's may not have been read yet:
-  // an output that overlaps them is refused
-  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model);
-  const struct { const void* p; size_t rows; const char* name; } outs[3] = {{a->x_new, nx, "x_new"}, {a->gx, nx, "gx"}, {a->A, nx * nx, "A"}};
-  const struct { const void* p; const char* name; } ins[2] = {{a->state, "state"}, {a->gbar, "gbar"}};
-  for (const auto& o : outs)
-    for (const auto& in : ins) {
-      if (!o.p || !in.p) continue;
-      const char *o0 = (const char*)o.p, *i0 = (const char*)in.p;
-      if (o0 < i0 + nx * row && i0 < o0 + o.rows * row)
-        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", o.name, in.name);
-    }
-  return CPMPC_OK;
+  rc = check_model_dtype_batch(model, dtype, B);
+  if (rc) return rc;
+  const size_t nx = (size_t)model_nx(model);
+  const ArraySpan outs[3] = {{a->x_new, nx, "x_new"}, {a->gx, nx, "gx"}, {a->A, nx * nx, "A"}};
+  const ArraySpan ins[2] = {{a->state, nx, "state"}, {a->gbar, nx, "gbar"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }
 
 // Simulator::Step with A = dx+/dx and Bu = dx+/du, or their products with a cotangent (sim_jac_kernels.hpp)
@@ -853,15 +898,9 @@ extern "C" int cpmpc_sim_step_jac_batch(int model, int dtype, int64_t B, const d
                                         const cpmpc_sim_jac* a, void* stream) {
   int rc = check_sim_jac_args(model, dtype, B, dyn_shared_host, dt, a);
   if (rc) return rc;
-  rc = current_device_ok();
-  if (rc) return rc;
-  int n_sub = 0;
-  double h_last = 0.0;
-  rc = sim_sub_steps(dt, &n_sub, &h_last);
-  if (rc) return rc;
-  engine_for(dtype, model)->sim_jac(B, dyn_shared_host, n_sub, h_last, a, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return CPMPC_OK;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_jac(B, dyn_shared_host, n_sub, h_last, a, (hipStream_t)stream);
+  });
 }
 
 // The plant step with per-problem parameters: dyn == NULL is cpmpc_sim_step_batch_model itself
@@ -870,59 +909,39 @@ extern "C" int cpmpc_sim_step_dyn_batch(int model, int dtype, int64_t B, const d
                                         void* stream) {
   if (!dyn) return cpmpc_sim_step_batch_model(model, dtype, B, dyn_shared_host, dt, u, fext_host, fext, state, stream);
   if (!u || !state) return fail(CPMPC_ERR_INVALID_ARG, "null argument");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
-  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
-  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
-  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
-  {  // the kernel updates the state in place while other lanes still read their parameters
-    const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4);
-    const char *s0 = (const char*)state, *d0 = (const char*)dyn;
-    if (s0 < d0 + (size_t)cpmpc_model_num_params(model) * row && d0 < s0 + (size_t)model_nx(model) * row)
-      return fail(CPMPC_ERR_INVALID_ARG, "state overlaps dyn, which the call only reads (give another array)");
-  }
-  int rc = current_device_ok();
+  int rc = check_plant_dt(dt);
   if (rc) return rc;
-  int n_sub = 0;
-  double h_last = 0.0;
-  rc = sim_sub_steps(dt, &n_sub, &h_last);
+  rc = check_model_dtype_batch(model, dtype, B);
   if (rc) return rc;
-  if (n_sub == 0) return CPMPC_OK;
-  engine_for(dtype, model)->sim_dyn(B, dyn, fext_host, fext, n_sub, h_last, u, state, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return CPMPC_OK;
+  // the kernel updates the state in place while other lanes still read their parameters
+  const ArraySpan outs[1] = {{state, (size_t)model_nx(model), "state"}};
+  const ArraySpan ins[1] = {{dyn, (size_t)model_np(model), "dyn"}};
+  rc = check_no_overlap(outs, ins, row_bytes(dtype, B));
+  if (rc) return rc;
+  return run_plant_call(dt, true, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_dyn(B, dyn, fext_host, fext, n_sub, h_last, u, state, (hipStream_t)stream);
+  });
 }
 
 // The argument checks of cpmpc_sim_step_param_jac_batch (no device needed)
 static int check_sim_param_jac_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
                                     const cpmpc_sim_param_jac* a) {
   if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_param_jac)");
-  if (a->struct_size != sizeof(cpmpc_sim_param_jac))
-    return fail(CPMPC_ERR_INVALID_ARG,
-                "cpmpc_sim_param_jac.struct_size is %llu, this library's is %zu (set it to sizeof(cpmpc_sim_param_jac))",
-                (unsigned long long)a->struct_size, sizeof(cpmpc_sim_param_jac));
+  int rc = check_struct_size("cpmpc_sim_param_jac", a->struct_size, sizeof(cpmpc_sim_param_jac));
+  if (rc) return rc;
   if (!a->state || !a->u) return fail(CPMPC_ERR_INVALID_ARG, "null argument (state, u)");
   if (!dyn_shared_host && !a->dyn) return fail(CPMPC_ERR_INVALID_ARG, "null argument (neither dyn_shared_host nor dyn is given)");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  rc = check_plant_dt(dt);
+  if (rc) return rc;
   if ((a->gp || a->gx || a->gu) && !a->gbar) return fail(CPMPC_ERR_INVALID_ARG, "gp / gx / gu are given without gbar");
   if (a->gbar && !a->gp && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "gbar is given with none of gp, gx, gu");
   if (!a->x_new && !a->P && !a->gp && !a->gx && !a->gu) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
-  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
-  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
-  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
-  // lanes run in any order: an output that overlaps what another lane has yet to read is refused
-  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model);
-  const size_t np = (size_t)cpmpc_model_num_params(model);
-  const struct { const void* p; size_t rows; const char* name; } outs[5] = {
-      {a->x_new, nx, "x_new"}, {a->P, nx * np, "P"}, {a->gp, np, "gp"}, {a->gx, nx, "gx"}, {a->gu, 1, "gu"}};
-  const struct { const void* p; size_t rows; const char* name; } ins[3] = {{a->state, nx, "state"}, {a->gbar, nx, "gbar"}, {a->dyn, np, "dyn"}};
-  for (const auto& o : outs)
-    for (const auto& in : ins) {
-      if (!o.p || !in.p) continue;
-      const char *o0 = (const char*)o.p, *i0 = (const char*)in.p;
-      if (o0 < i0 + in.rows * row && i0 < o0 + o.rows * row)
-        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", o.name, in.name);
-    }
-  return CPMPC_OK;
+  rc = check_model_dtype_batch(model, dtype, B);
+  if (rc) return rc;
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model);
+  const ArraySpan outs[5] = {{a->x_new, nx, "x_new"}, {a->P, nx * np, "P"}, {a->gp, np, "gp"}, {a->gx, nx, "gx"}, {a->gu, 1, "gu"}};
+  const ArraySpan ins[3] = {{a->state, nx, "state"}, {a->gbar, nx, "gbar"}, {a->dyn, np, "dyn"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }
 
 // Simulator::Step with P = dx+/dp, or its product with a cotangent, and the state / control cotangents (sim_param_kernels.hpp)
@@ -930,15 +949,9 @@ extern "C" int cpmpc_sim_step_param_jac_batch(int model, int dtype, int64_t B, c
                                               const cpmpc_sim_param_jac* a, void* stream) {
   int rc = check_sim_param_jac_args(model, dtype, B, dyn_shared_host, dt, a);
   if (rc) return rc;
-  rc = current_device_ok();
-  if (rc) return rc;
-  int n_sub = 0;
-  double h_last = 0.0;
-  rc = sim_sub_steps(dt, &n_sub, &h_last);
-  if (rc) return rc;
-  engine_for(dtype, model)->sim_param_jac(B, dyn_shared_host, n_sub, h_last, a, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return CPMPC_OK;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_param_jac(B, dyn_shared_host, n_sub, h_last, a, (hipStream_t)stream);
+  });
 }
 
 // ---- the plant over T ticks and its adjoint (sim_rollout_kernels.hpp) ------------------------------------------------
@@ -946,35 +959,14 @@ extern "C" int cpmpc_sim_step_param_jac_batch(int model, int dtype, int64_t B, c
 static int check_rollout_common(const char* what, uint64_t struct_size, size_t size_here, const void* x0, const void* u,
                                 const double* dyn_shared_host, const void* dyn, double dt, int T, int model, int dtype,
                                 int64_t B) {
-  if (struct_size != size_here)
-    return fail(CPMPC_ERR_INVALID_ARG, "%s.struct_size is %llu, this library's is %zu (set it to sizeof(%s))", what,
-                (unsigned long long)struct_size, size_here, what);
+  int rc = check_struct_size(what, struct_size, size_here);
+  if (rc) return rc;
   if (!x0 || !u) return fail(CPMPC_ERR_INVALID_ARG, "null argument (x0, u)");
   if (!dyn_shared_host && !dyn) return fail(CPMPC_ERR_INVALID_ARG, "null argument (neither dyn_shared_host nor dyn is given)");
-  if (!(dt >= 0.0) || !std::isfinite(dt)) return fail(CPMPC_ERR_INVALID_ARG, "dt must be finite and >= 0 (simulator.cc:13)");
+  rc = check_plant_dt(dt);
+  if (rc) return rc;
   if (T < 1) return fail(CPMPC_ERR_INVALID_ARG, "T must be >= 1");
-  if (model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) return fail(CPMPC_ERR_INVALID_ARG, "unknown model");
-  if (dtype != CPMPC_F32 && dtype != CPMPC_F64) return fail(CPMPC_ERR_INVALID_ARG, "bad dtype");
-  if (B < 1) return fail(CPMPC_ERR_INVALID_ARG, "B must be >= 1");
-  return CPMPC_OK;
-}
-
-struct RolloutSpan {
-  const void* p;
-  size_t rows;  // of B numbers each
-  const char* name;
-};
-// lanes run in any order: an output that overlaps what another lane has yet to read is refused
-static int check_rollout_overlap(const RolloutSpan* outs, int n_out, const RolloutSpan* ins, int n_in, size_t row) {
-  for (int o = 0; o < n_out; ++o)
-    for (int i = 0; i < n_in; ++i) {
-      if (!outs[o].p || !ins[i].p) continue;
-      const char *o0 = (const char*)outs[o].p, *i0 = (const char*)ins[i].p;
-      if (o0 < i0 + ins[i].rows * row && i0 < o0 + outs[o].rows * row)
-        return fail(CPMPC_ERR_INVALID_ARG, "%s overlaps %s, which the call only reads (give another array)", outs[o].name,
-                    ins[i].name);
-    }
-  return CPMPC_OK;
+  return check_model_dtype_batch(model, dtype, B);
 }
 
 static int check_sim_rollout_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
@@ -984,26 +976,19 @@ static int check_sim_rollout_args(int model, int dtype, int64_t B, const double*
                                 a->dyn, dt, T, model, dtype, B);
   if (rc) return rc;
   if (!a->xs && !a->x_final) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
-  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model), nt = (size_t)T;
-  const size_t np = (size_t)cpmpc_model_num_params(model);
-  const RolloutSpan outs[2] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}};
-  const RolloutSpan ins[4] = {{a->x0, nx, "x0"}, {a->u, nt, "u"}, {a->fext, 4, "fext"}, {a->dyn, np, "dyn"}};
-  return check_rollout_overlap(outs, 2, ins, 4, row);
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  const ArraySpan outs[2] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}};
+  const ArraySpan ins[4] = {{a->x0, nx, "x0"}, {a->u, nt, "u"}, {a->fext, 4, "fext"}, {a->dyn, np, "dyn"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }
 
 extern "C" int cpmpc_sim_rollout_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                        const cpmpc_sim_rollout* a, void* stream) {
   int rc = check_sim_rollout_args(model, dtype, B, dyn_shared_host, dt, T, a);
   if (rc) return rc;
-  rc = current_device_ok();
-  if (rc) return rc;
-  int n_sub = 0;
-  double h_last = 0.0;
-  rc = sim_sub_steps(dt, &n_sub, &h_last);
-  if (rc) return rc;
-  engine_for(dtype, model)->sim_rollout(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return CPMPC_OK;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_rollout(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
 }
 
 static int check_sim_rollout_vjp_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
@@ -1015,29 +1000,22 @@ static int check_sim_rollout_vjp_args(int model, int dtype, int64_t B, const dou
   if (!a->g_x0 && !a->g_u && !a->g_p) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
   if (!a->gbar && !a->gbar_final) return fail(CPMPC_ERR_INVALID_ARG, "neither gbar nor gbar_final is given");
   if (T > 1 && !a->xs) return fail(CPMPC_ERR_INVALID_ARG, "xs (a forward call's checkpoints) is required when T > 1");
-  const size_t row = (size_t)B * (dtype == CPMPC_F64 ? 8 : 4), nx = (size_t)model_nx(model), nt = (size_t)T;
-  const size_t np = (size_t)cpmpc_model_num_params(model);
-  const RolloutSpan outs[3] = {{a->g_x0, nx, "g_x0"}, {a->g_u, nt, "g_u"}, {a->g_p, np, "g_p"}};
-  const RolloutSpan ins[7] = {{a->x0, nx, "x0"},           {a->u, nt, "u"},
-                              {a->fext, 4, "fext"},        {a->dyn, np, "dyn"},
-                              {a->xs, nt * nx, "xs"},      {a->gbar, nt * nx, "gbar"},
-                              {a->gbar_final, nx, "gbar_final"}};
-  return check_rollout_overlap(outs, 3, ins, 7, row);
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  const ArraySpan outs[3] = {{a->g_x0, nx, "g_x0"}, {a->g_u, nt, "g_u"}, {a->g_p, np, "g_p"}};
+  const ArraySpan ins[7] = {{a->x0, nx, "x0"},           {a->u, nt, "u"},
+                            {a->fext, 4, "fext"},        {a->dyn, np, "dyn"},
+                            {a->xs, nt * nx, "xs"},      {a->gbar, nt * nx, "gbar"},
+                            {a->gbar_final, nx, "gbar_final"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }
 
 extern "C" int cpmpc_sim_rollout_vjp_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                            const cpmpc_sim_rollout_vjp* a, void* stream) {
   int rc = check_sim_rollout_vjp_args(model, dtype, B, dyn_shared_host, dt, T, a);
   if (rc) return rc;
-  rc = current_device_ok();
-  if (rc) return rc;
-  int n_sub = 0;
-  double h_last = 0.0;
-  rc = sim_sub_steps(dt, &n_sub, &h_last);
-  if (rc) return rc;
-  engine_for(dtype, model)->sim_rollout_vjp(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return CPMPC_OK;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_rollout_vjp(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------

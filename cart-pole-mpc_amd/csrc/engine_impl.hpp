@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 
 #include "engine.hpp"
 #include "mpc_kernels.hpp"
@@ -522,7 +523,35 @@ static void sim_jac_impl(int64_t B, const double* dyn_shared_host, int n_sub, do
 }
 
 // ---- per-problem plant parameters, and the plant step's derivative in them (sim_param_kernels.hpp) ---------------------
-// dyn [NP][B] on the device: the PER_LANE instantiations of the two plant kernels
+// dyn [NP][B] on the device: the PER_LANE instantiations of the plant kernels.  A call that takes either set chooses the
+// instantiation once, f(std::true_type) or f(std::false_type), and writes its argument list once:
+template <typename F>
+static void with_per_lane(bool per_lane, F f) {
+  if (per_lane) f(std::true_type{});
+  else f(std::false_type{});
+}
+// ... the kernels' first argument (mpc_kernels.hpp: PlantConsts): the per-problem array, or the shared set folded here
+template <typename R, typename M, bool PER_LANE>
+static typename PlantConsts<R, M, PER_LANE>::Arg plant_consts_arg(const double* dyn_shared_host, const void* dyn) {
+  if constexpr (PER_LANE) return (const R*)dyn;
+  else return M::template make<double>(dyn_shared_host);
+}
+// ... and for the kernels that want the raw parameters too: the shared set folded and in R, or zeros that PER_LANE never reads
+template <typename R, typename M>
+struct SharedPlantParams {
+  typename M::Consts k{};
+  RawParams<R, M::NP> raw{};
+};
+template <typename R, typename M, bool PER_LANE>
+static SharedPlantParams<R, M> shared_plant_params(const double* dyn_shared_host) {
+  SharedPlantParams<R, M> s;
+  if constexpr (!PER_LANE) {
+    s.k = M::template make<double>(dyn_shared_host);
+    for (int i = 0; i < M::NP; ++i) s.raw.p[i] = (R)dyn_shared_host[i];
+  }
+  return s;
+}
+
 template <typename R, typename M>
 static void sim_dyn_impl(int64_t B, const void* dyn, const double* fext_host, const void* fext, int n_sub, double h_last,
                          const void* u, void* state, hipStream_t stream) {
@@ -545,13 +574,8 @@ static void launch_param_groups(int64_t B, const double* dyn_shared_host, int n_
   constexpr int NG = (J0 + W <= M::NP) ? W : M::NP - J0;
   R* x_new = (J0 == 0) ? (R*)a->x_new : nullptr;  // the primal step is every group's; the first one writes it
   if (x_new || a->P || a->gp) {
-    typename M::Consts k{};
-    RawParams<R, M::NP> raw{};
-    if constexpr (!PER_LANE) {
-      k = M::template make<double>(dyn_shared_host);
-      for (int i = 0; i < M::NP; ++i) raw.p[i] = (R)dyn_shared_host[i];
-    }
-    hipLaunchKernelGGL((sim_param_jac_kernel<R, M, J0, NG, PER_LANE>), grid_for(B), dim3(64), 0, stream, B, k, raw,
+    const SharedPlantParams<R, M> sp = shared_plant_params<R, M, PER_LANE>(dyn_shared_host);
+    hipLaunchKernelGGL((sim_param_jac_kernel<R, M, J0, NG, PER_LANE>), grid_for(B), dim3(64), 0, stream, B, sp.k, sp.raw,
                        (const R*)a->dyn, ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last,
                        (const R*)a->state, (const R*)a->u, x_new, (R*)a->P, (const R*)(a->gp ? a->gbar : nullptr), (R*)a->gp);
   }
@@ -562,54 +586,39 @@ static void launch_param_groups(int64_t B, const double* dyn_shared_host, int n_
 template <typename R, typename M>
 static void sim_param_jac_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, const cpmpc_sim_param_jac* a,
                                hipStream_t stream) {
-  if (a->gx || a->gu) {
-    if (a->dyn)
-      hipLaunchKernelGGL((sim_jac_kernel<R, M, true>), grid_for(B), dim3(64), 0, stream, B, (const R*)a->dyn,
-                         ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, (const R*)a->state,
-                         (const R*)a->u, (R*)nullptr, (R*)nullptr, (R*)nullptr, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
-    else
-      hipLaunchKernelGGL((sim_jac_kernel<R, M>), grid_for(B), dim3(64), 0, stream, B, M::template make<double>(dyn_shared_host),
-                         ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, (const R*)a->state,
-                         (const R*)a->u, (R*)nullptr, (R*)nullptr, (R*)nullptr, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
-  }
-  if (a->x_new || a->P || a->gp) {
-    if (a->dyn) launch_param_groups<R, M, 0, true>(B, dyn_shared_host, n_sub, h_last, a, stream);
-    else launch_param_groups<R, M, 0, false>(B, dyn_shared_host, n_sub, h_last, a, stream);
-  }
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    if (a->gx || a->gu)
+      hipLaunchKernelGGL((sim_jac_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                         plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host),
+                         (const R*)a->fext, n_sub, (R)h_last, (const R*)a->state, (const R*)a->u, (R*)nullptr, (R*)nullptr,
+                         (R*)nullptr, (const R*)a->gbar, (R*)a->gx, (R*)a->gu);
+    if (a->x_new || a->P || a->gp) launch_param_groups<R, M, 0, PL>(B, dyn_shared_host, n_sub, h_last, a, stream);
+  });
 }
 
 // ---- the plant over T ticks and its adjoint, one launch each (sim_rollout_kernels.hpp) ----------------------------------
 template <typename R, typename M>
 static void sim_rollout_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                              const cpmpc_sim_rollout* a, hipStream_t stream) {
-  if (a->dyn)
-    hipLaunchKernelGGL((sim_rollout_kernel<R, M, true>), grid_for(B), dim3(64), 0, stream, B, (const R*)a->dyn,
-                       ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, T, (const R*)a->x0,
-                       (const R*)a->u, (R*)a->xs, (R*)a->x_final);
-  else
-    hipLaunchKernelGGL((sim_rollout_kernel<R, M, false>), grid_for(B), dim3(64), 0, stream, B,
-                       M::template make<double>(dyn_shared_host), ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub,
-                       (R)h_last, T, (const R*)a->x0, (const R*)a->u, (R*)a->xs, (R*)a->x_final);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    hipLaunchKernelGGL((sim_rollout_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                       plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u, (R*)a->xs, (R*)a->x_final);
+  });
 }
 
-template <typename R, typename M, bool PER_LANE>
-static void launch_rollout_vjp(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
-                               const cpmpc_sim_rollout_vjp* a, hipStream_t stream) {
-  typename M::Consts k{};
-  RawParams<R, M::NP> raw{};
-  if constexpr (!PER_LANE) {
-    k = M::template make<double>(dyn_shared_host);
-    for (int i = 0; i < M::NP; ++i) raw.p[i] = (R)dyn_shared_host[i];
-  }
-  hipLaunchKernelGGL((sim_rollout_vjp_kernel<R, M, PER_LANE>), grid_for(B), dim3(64), 0, stream, B, k, raw, (const R*)a->dyn,
-                     ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u,
-                     (const R*)a->xs, (const R*)a->gbar, (const R*)a->gbar_final, (R*)a->g_x0, (R*)a->g_u, (R*)a->g_p);
-}
 template <typename R, typename M>
 static void sim_rollout_vjp_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                                  const cpmpc_sim_rollout_vjp* a, hipStream_t stream) {
-  if (a->dyn) launch_rollout_vjp<R, M, true>(B, dyn_shared_host, n_sub, h_last, T, a, stream);
-  else launch_rollout_vjp<R, M, false>(B, dyn_shared_host, n_sub, h_last, T, a, stream);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    const SharedPlantParams<R, M> sp = shared_plant_params<R, M, PL>(dyn_shared_host);
+    hipLaunchKernelGGL((sim_rollout_vjp_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B, sp.k, sp.raw, (const R*)a->dyn,
+                       ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u,
+                       (const R*)a->xs, (const R*)a->gbar, (const R*)a->gbar_final, (R*)a->g_x0, (R*)a->g_u, (R*)a->g_p);
+  });
 }
 
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------

@@ -1364,7 +1364,31 @@ struct PlantConsts<R, M, true> {
   }
 };
 
-// Simulator::Step (simulator.cc:11-36): fixed 1 ms sub-steps, angles wrapped after each.
+// The external forces of a lane: `fe` holds the shared set's and -- where fext [4][B] is given -- takes the lane's own (row 1
+// is not read).  In place: returned by value, the same loads come out as other instructions in some instantiations.
+template <typename R>
+__device__ __forceinline__ void load_ext_force(const R* fext, int64_t B, int64_t p, ExtForce<R>& fe) {
+  if (fext) {
+    fe.fbx = fext[p];
+    fe.fmx = fext[2 * B + p];
+    fe.fmy = fext[3 * B + p];
+  }
+}
+
+// Sub-step i of n_sub of one tick of the plant, Simulator::Step (simulator.cc:11-36): an RK4 step of 1 ms, the last one of
+// h_last, the control held, the angles wrapped.  The host evaluates the reference's `while (dt > 0) { SubStep(min(dt, 0.001));
+// dt -= 0.001; }` in double and passes the count and the last step, so f32 and f64 take the same sub-steps.  `chain` is the
+// tick's: a fresh StepCache before sub-step 0.
+template <typename R, typename M>
+__device__ __forceinline__ void plant_sub_step(const typename M::Consts& k, const ExtForce<R>& fe, int i, int n_sub, R h_last,
+                                               R uu, R (&xs)[M::NX], typename M::StepCache& chain) {
+  const R internal_dt = R(0.001);
+  const R h = (i + 1 == n_sub) ? h_last : internal_dt;
+  if (i % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
+  rk4_step_m<R, M, true>(k, h, xs, uu, fe, chain);
+  wrap_angles<R, M>(xs);
+}
+
 template <typename R, typename M, bool PER_LANE = false>
 __global__ __launch_bounds__(64) void sim_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg, ExtForce<R> fe_shared,
                                                   const R* fext, int n_sub, R h_last, const R* u, R* state) {
@@ -1373,25 +1397,13 @@ __global__ __launch_bounds__(64) void sim_kernel(int64_t B, typename PlantConsts
   if (p >= B) return;
   const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
   ExtForce<R> fe = fe_shared;
-  if (fext) {
-    fe.fbx = fext[p];
-    fe.fmx = fext[2 * B + p];
-    fe.fmy = fext[3 * B + p];
-  }
+  load_ext_force<R>(fext, B, p, fe);
   R xs[NX];
 #pragma unroll
   for (int t = 0; t < NX; ++t) xs[t] = state[t * B + p];
   const R uu = u[p];
-  // the host evaluates the reference's `while (dt > 0) { SubStep(min(dt, 0.001)); dt -= 0.001; }`
-  // in double and passes the count and the last step, so f32 and f64 take the same sub-steps
-  const R internal_dt = R(0.001);
   typename M::StepCache chain;
-  for (int i = 0; i < n_sub; ++i) {
-    const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-    if (i % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
-    rk4_step_m<R, M, true>(k, h, xs, uu, fe, chain);
-    wrap_angles<R, M>(xs);
-  }
+  for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
 #pragma unroll
   for (int t = 0; t < NX; ++t) state[t * B + p] = xs[t];
 }

@@ -4,7 +4,8 @@
 // of the whole step, accumulated FORWARD over the sub-steps as linearize_kernel accumulates an interval:
 //     Phi <- A_i Phi,   gamma <- A_i gamma + B_i,   Phi_0 = I, gamma_0 = 0,
 // with A_i, B_i from rk4_step_jac_m (external forces included).  The wrap has unit derivative.  Nothing per sub-step is
-// stored, whatever their number.  One problem per lane, no LDS; the state is read only.
+// stored, whatever their number.  One problem per lane, no LDS; the state is read only.  The accumulation over a tick is
+// sim_jac_tick.inc and the product Phi^T g is sim_jac_vjp.inc: texts that pass A of sim_rollout_vjp_kernel includes too.
 //
 // Outputs, each written only where its pointer is given (a wave-uniform choice): x_new [NX][B], A = Phi [NX*NX][B] (element
 // (r, c) at field r*NX + c, the layout of rk4_kernel), Bu = gamma [NX][B] and, for a cotangent gbar [NX][B], the products
@@ -29,52 +30,13 @@ __global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename PlantCo
   if (p >= B) return;
   const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
   ExtForce<R> fe = fe_shared;
-  if (fext) {
-    fe.fbx = fext[p];
-    fe.fmx = fext[2 * B + p];
-    fe.fmy = fext[3 * B + p];
-  }
+  load_ext_force<R>(fext, B, p, fe);
   R xs[NX];
 #pragma unroll
   for (int t = 0; t < NX; ++t) xs[t] = state[t * B + p];
   const R uu = u[p];
 
-  R Phi[NX][NX], gam[NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r) {
-#pragma unroll
-    for (int c = 0; c < NX; ++c)
-      if (!((TRIV >> c) & 1u)) Phi[r][c] = (r == c) ? R(1) : R(0);
-    gam[r] = R(0);
-  }
-  R t_sum = R(0);  // entry (c - NQ, c) of a trivial velocity column: the sub-steps' lengths added up
-
-  const R internal_dt = R(0.001);
-  typename M::StepCache chain;
-#pragma unroll 1
-  for (int i = 0; i < n_sub; ++i) {
-    const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-    R A[NX][NX], Bv[NX];
-    rk4_step_jac_m<R, M, true>(k, h, xs, uu, fe, A, Bv, chain);
-    wrap_angles<R, M>(xs);
-#pragma unroll
-    for (int c = 0; c < NX; ++c) {
-      if ((TRIV >> c) & 1u) continue;
-      R v[NX], y[NX];
-#pragma unroll
-      for (int m = 0; m < NX; ++m) v[m] = Phi[m][c];
-      step_jac_apply<R, M>(A, h, v, y);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) Phi[r][c] = y[r];
-    }
-    {
-      R y[NX];
-      step_jac_apply<R, M>(A, h, gam, y);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) gam[r] = y[r] + Bv[r];
-    }
-    if (TRIV != 0u) t_sum += h;
-  }
+#include "sim_jac_tick.inc"  // Phi, gam, t_sum of the tick; xs becomes x+
 
   if (x_new)
 #pragma unroll
@@ -103,20 +65,11 @@ __global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename PlantCo
       if (gu) gu[p] = R(0);
       return;
     }
-    if (gx)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R acc;
-        if ((TRIV >> c) & 1u) {
-          acc = g[c];
-          if (c >= NQ) acc += t_sum * g[c - NQ];
-        } else {
-          acc = Phi[0][c] * g[0];
-#pragma unroll
-          for (int r = 1; r < NX; ++r) acc += Phi[r][c] * g[r];
-        }
-        gx[c * B + p] = acc;
-      }
+    if (gx) {
+#define CPMPC_PHI_T_G(c) gx[(c) * B + p]
+#include "sim_jac_vjp.inc"
+#undef CPMPC_PHI_T_G
+    }
     if (gu) {
       R acc = gam[0] * g[0];
 #pragma unroll

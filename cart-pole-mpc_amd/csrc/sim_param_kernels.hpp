@@ -16,6 +16,8 @@
 // The parameter columns are processed in compile-time groups [J0, J0 + NG), one launch per group, each recomputing the primal
 // step (engine_impl.hpp: sim_param_jac_impl; the group widths are the largest without scratch).  With a
 // cotangent gbar [NX][B] a group contracts its rows of gp = P^T gbar [NP][B] in registers and P never goes to memory.
+// The tangents of a tick are sim_param_tick.inc and the raw parameters' load is sim_param_load.inc: texts that pass B of
+// sim_rollout_vjp_kernel includes too.
 #pragma once
 #include "double_pendulum_param_gen.hpp"
 #include "sim_jac_kernels.hpp"
@@ -437,40 +439,17 @@ __global__ __launch_bounds__(64) void sim_param_jac_kernel(int64_t B, typename M
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B) return;
   ExtForce<R> fe = fe_shared;
-  if (fext) {
-    fe.fbx = fext[p];
-    fe.fmx = fext[2 * B + p];
-    fe.fmy = fext[3 * B + p];
-  }
+  load_ext_force<R>(fext, B, p, fe);
   R prm[NP];
   typename M::Consts k = k_shared;
-  if constexpr (PER_LANE) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) prm[i] = dyn[i * B + p];
-    k = M::template make<R>(prm);
-  } else {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) prm[i] = raw.p[i];
-  }
+#include "sim_param_load.inc"
+  if constexpr (PER_LANE) k = M::template make<R>(prm);
   R xs[NX];
 #pragma unroll
   for (int t = 0; t < NX; ++t) xs[t] = state[t * B + p];
   const R uu = u[p];
 
-  R T[NG][NX];
-#pragma unroll
-  for (int gI = 0; gI < NG; ++gI)
-#pragma unroll
-    for (int r = 0; r < NX; ++r) T[gI][r] = R(0);
-
-  const R internal_dt = R(0.001);
-  typename M::StepCache chain;
-#pragma unroll 1
-  for (int i = 0; i < n_sub; ++i) {
-    const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-    rk4_step_param_m<R, M, true, J0, NG>(k, prm, h, xs, uu, fe, T, chain);
-    wrap_angles<R, M>(xs);
-  }
+#include "sim_param_tick.inc"  // Tn of the tick; xs becomes x+
 
   if (x_new)
 #pragma unroll
@@ -479,7 +458,7 @@ __global__ __launch_bounds__(64) void sim_param_jac_kernel(int64_t B, typename M
 #pragma unroll
     for (int gI = 0; gI < NG; ++gI)
 #pragma unroll
-      for (int r = 0; r < NX; ++r) P[(r * NP + J0 + gI) * B + p] = T[gI][r];
+      for (int r = 0; r < NX; ++r) P[(r * NP + J0 + gI) * B + p] = Tn[gI][r];
   if (gp) {
     if (n_sub == 0) {  // the identity map has no parameters: zeros, not products of zeros with the cotangent
 #pragma unroll
@@ -491,9 +470,9 @@ __global__ __launch_bounds__(64) void sim_param_jac_kernel(int64_t B, typename M
     for (int r = 0; r < NX; ++r) g[r] = gbar[r * B + p];
 #pragma unroll
     for (int gI = 0; gI < NG; ++gI) {
-      R acc = T[gI][0] * g[0];
+      R acc = Tn[gI][0] * g[0];
 #pragma unroll
-      for (int r = 1; r < NX; ++r) acc += T[gI][r] * g[r];
+      for (int r = 1; r < NX; ++r) acc += Tn[gI][r] * g[r];
       gp[(J0 + gI) * B + p] = acc;
     }
   }

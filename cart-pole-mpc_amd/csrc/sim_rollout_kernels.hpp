@@ -4,8 +4,9 @@
 // h_last, the control held over the tick, the pole angles wrapped after each sub-step.  dt, the external forces and the
 // dynamics parameters are those of every tick.  One problem per lane, no LDS; the tick loop stays on the device.
 //
-// sim_rollout_kernel: the tick body is sim_kernel's loop; after tick t it stores x_{t+1} to xs [T][NX][B] (field t*NX + r)
-// and after the last one to x_final [NX][B], each where its pointer is given (a wave-uniform choice).
+// sim_rollout_kernel: a tick is n_sub calls of plant_sub_step (mpc_kernels.hpp), the function sim_kernel's loop calls; after
+// tick t it stores x_{t+1} to xs [T][NX][B] (field t*NX + r) and after the last one to x_final [NX][B], each where its pointer
+// is given (a wave-uniform choice).
 //
 // sim_rollout_vjp_kernel: REVERSE over the ticks, FORWARD inside a tick.  With the cotangents gbar [T][NX][B] on every
 // x_{t+1} and / or gbar_final [NX][B] on x_T,
@@ -13,14 +14,17 @@
 //     for t = T-1 .. 0:
 //         lambda += gbar[t]  (+= gbar_final at t = T-1)
 //         x_t = (t == 0) ? x0 : xs[t-1]                       -- a forward call's checkpoints; row T-1 is never loaded
-//         pass B: sim_param_jac_kernel's sub-step loop from x_t, every column -> gp += P^T lambda   (where g_p is given)
-//         pass A: sim_jac_kernel's sub-step loop from x_t      -> g_u[t] = gamma . lambda,  lambda <- Phi^T lambda
+//         pass B: sim_param_tick.inc from x_t, every column         -> gp += P^T lambda   (where g_p is given)
+//         pass A: sim_jac_tick.inc from x_t, then sim_jac_vjp.inc    -> g_u[t] = gamma . lambda,  lambda <- Phi^T lambda
 //     g_x0 = lambda, g_p = gp
 // lambda and gp stay in registers across the ticks.  The passes run one after the other (B before A, so that one copy of
 // lambda serves both), so what is live at once is the larger of the two existing kernels' sets plus lambda and gp.
 // Nothing per sub-step is stored; the adjoint of RK4 inside a tick is not built.  n_sub == 0 is the identity
 // map: g_x0 is the cotangents added up in that order, g_u and g_p are zeros.  Not differentiated: the external forces and
 // dt; the wrap has unit derivative.
+//
+// The two passes are the texts sim_param_jac_kernel and sim_jac_kernel are made of, included here (the .inc files say what
+// they expect in scope); written as functions the same statements compile to other registers and spills.
 #pragma once
 #include "sim_param_kernels.hpp"
 
@@ -35,26 +39,16 @@ __global__ __launch_bounds__(64) void sim_rollout_kernel(int64_t B, typename Pla
   if (p >= B) return;
   const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
   ExtForce<R> fe = fe_shared;
-  if (fext) {
-    fe.fbx = fext[p];
-    fe.fmx = fext[2 * B + p];
-    fe.fmy = fext[3 * B + p];
-  }
+  load_ext_force<R>(fext, B, p, fe);
   R xs[NX];
 #pragma unroll
   for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
-  const R internal_dt = R(0.001);
 #pragma unroll 1
   for (int t = 0; t < T; ++t) {
     const R uu = u[(int64_t)t * B + p];
     typename M::StepCache chain;
 #pragma unroll 1
-    for (int i = 0; i < n_sub; ++i) {
-      const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-      if (i % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
-      rk4_step_m<R, M, true>(k, h, xs, uu, fe, chain);
-      wrap_angles<R, M>(xs);
-    }
+    for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
     if (xs_out)
 #pragma unroll
       for (int r = 0; r < NX; ++r) xs_out[((int64_t)t * NX + r) * B + p] = xs[r];
@@ -64,8 +58,8 @@ __global__ __launch_bounds__(64) void sim_rollout_kernel(int64_t B, typename Pla
     for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
 }
 
-// PER_LANE: the parameters are dyn [NP][B], read per lane, and the constants are M::make<R> of them in the kernel, as
-// sim_param_jac_kernel does; else `k_shared` and `raw` are the shared set's.
+// PER_LANE: the parameters are dyn [NP][B], read per lane (sim_param_load.inc), and the constants are M::make<R> of them in
+// the kernel, as sim_param_jac_kernel does; else `k_shared` and `raw` are the shared set's.
 template <typename R, typename M, bool PER_LANE>
 __global__ __launch_bounds__(64) void sim_rollout_vjp_kernel(int64_t B, typename M::Consts k_shared, RawParams<R, M::NP> raw,
                                                               const R* dyn, ExtForce<R> fe_shared, const R* fext, int n_sub,
@@ -76,16 +70,11 @@ __global__ __launch_bounds__(64) void sim_rollout_vjp_kernel(int64_t B, typename
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B) return;
   ExtForce<R> fe = fe_shared;
-  if (fext) {
-    fe.fbx = fext[p];
-    fe.fmx = fext[2 * B + p];
-    fe.fmy = fext[3 * B + p];
-  }
+  load_ext_force<R>(fext, B, p, fe);
   typename M::Consts k = k_shared;
   if constexpr (PER_LANE) {
-    R prm[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) prm[i] = dyn[i * B + p];
+    R prm[NP];  // not held: pass B reads them again
+#include "sim_param_load.inc"
     k = M::template make<R>(prm);
   }
 
@@ -95,7 +84,6 @@ __global__ __launch_bounds__(64) void sim_rollout_vjp_kernel(int64_t B, typename
 #pragma unroll
   for (int j = 0; j < NP; ++j) gp[j] = R(0);
 
-  const R internal_dt = R(0.001);
 #pragma unroll 1
   for (int t = T - 1; t >= 0; --t) {
     if (gbar)
@@ -111,32 +99,16 @@ __global__ __launch_bounds__(64) void sim_rollout_vjp_kernel(int64_t B, typename
     const R* xt = (t == 0) ? x0 : xs_in + (int64_t)(t - 1) * NX * B;
     const R uu = u[(int64_t)t * B + p];
 
-    // ---- pass B: the parameter tangents of the tick, sim_param_jac_kernel's loop over every column.  It runs FIRST: it
-    // needs the lambda pass A replaces, and so no second copy of lambda is live beside the tangents ---------------------
+    // ---- pass B: the parameter tangents of the tick, every column.  It runs FIRST: it needs the lambda pass A replaces,
+    // and so no second copy of lambda is live beside the tangents --------------------------------------------------------
     if (g_p) {
       R prm[NP];  // the raw parameters, read here every tick rather than held across pass A
-      if constexpr (PER_LANE) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) prm[i] = dyn[i * B + p];
-      } else {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) prm[i] = raw.p[i];
-      }
+#include "sim_param_load.inc"
       R xs[NX];
 #pragma unroll
       for (int r = 0; r < NX; ++r) xs[r] = xt[r * B + p];
-      R Tn[NP][NX];
-#pragma unroll
-      for (int j = 0; j < NP; ++j)
-#pragma unroll
-        for (int r = 0; r < NX; ++r) Tn[j][r] = R(0);
-      typename M::StepCache chain;
-#pragma unroll 1
-      for (int i = 0; i < n_sub; ++i) {
-        const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-        rk4_step_param_m<R, M, true, 0, NP>(k, prm, h, xs, uu, fe, Tn, chain);
-        wrap_angles<R, M>(xs);
-      }
+      constexpr int J0 = 0, NG = NP;  // every column
+#include "sim_param_tick.inc"  // Tn [NP][NX] of the tick
 #pragma unroll
       for (int j = 0; j < NP; ++j) {
         R acc = Tn[j][0] * lam[0];
@@ -145,59 +117,17 @@ __global__ __launch_bounds__(64) void sim_rollout_vjp_kernel(int64_t B, typename
         gp[j] += acc;
       }
     }
-    // ---- pass A: Phi and gamma of the tick, sim_jac_kernel's loop; lambda <- Phi^T lambda ------------------------------
+    // ---- pass A: Phi and gamma of the tick; lambda <- Phi^T lambda -----------------------------------------------------
     {
-      R lam_new[NX];
       R xs[NX];
 #pragma unroll
       for (int r = 0; r < NX; ++r) xs[r] = xt[r * B + p];
-      R Phi[NX][NX], gam[NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) {
-#pragma unroll
-        for (int c = 0; c < NX; ++c)
-          if (!((TRIV >> c) & 1u)) Phi[r][c] = (r == c) ? R(1) : R(0);
-        gam[r] = R(0);
-      }
-      R t_sum = R(0);
-      typename M::StepCache chain;
-#pragma unroll 1
-      for (int i = 0; i < n_sub; ++i) {
-        const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-        R A[NX][NX], Bv[NX];
-        rk4_step_jac_m<R, M, true>(k, h, xs, uu, fe, A, Bv, chain);
-        wrap_angles<R, M>(xs);
-#pragma unroll
-        for (int c = 0; c < NX; ++c) {
-          if ((TRIV >> c) & 1u) continue;
-          R v[NX], y[NX];
-#pragma unroll
-          for (int m = 0; m < NX; ++m) v[m] = Phi[m][c];
-          step_jac_apply<R, M>(A, h, v, y);
-#pragma unroll
-          for (int r = 0; r < NX; ++r) Phi[r][c] = y[r];
-        }
-        {
-          R y[NX];
-          step_jac_apply<R, M>(A, h, gam, y);
-#pragma unroll
-          for (int r = 0; r < NX; ++r) gam[r] = y[r] + Bv[r];
-        }
-        if (TRIV != 0u) t_sum += h;
-      }
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R acc;
-        if ((TRIV >> c) & 1u) {
-          acc = lam[c];
-          if (c >= NQ) acc += t_sum * lam[c - NQ];
-        } else {
-          acc = Phi[0][c] * lam[0];
-#pragma unroll
-          for (int r = 1; r < NX; ++r) acc += Phi[r][c] * lam[r];
-        }
-        lam_new[c] = acc;
-      }
+#include "sim_jac_tick.inc"  // Phi, gam, t_sum of the tick
+      const R (&g)[NX] = lam;  // the cotangent of the tick, under the name sim_jac_vjp.inc reads
+      R lam_new[NX];
+#define CPMPC_PHI_T_G(c) lam_new[c]
+#include "sim_jac_vjp.inc"
+#undef CPMPC_PHI_T_G
       if (g_u) {
         R acc = gam[0] * lam[0];
 #pragma unroll
