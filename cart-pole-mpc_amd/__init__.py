@@ -19,7 +19,8 @@ def __getattr__(name):
     # torch-dependent pieces are imported lazily so the C-ABI can be inspected without torch
     if name in ("BatchOptimization", "BatchSimulator", "BatchOutputs", "ClosedLoop", "dynamics_batch", "rk4_batch",
                 "feedback_apply", "plan_update", "sim_step_jacobian", "sim_step_vjp", "sim_step",
-                "sim_step_param_jacobian", "sim_step_param_vjp", "sim_rollout_states", "sim_rollout_vjp", "sim_rollout"):
+                "sim_step_param_jacobian", "sim_step_param_vjp", "sim_rollout_states", "sim_rollout_vjp", "sim_rollout",
+                "sim_rollout_gauss_newton", "sim_identify"):
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

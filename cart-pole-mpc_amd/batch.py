@@ -1077,6 +1077,154 @@ def sim_rollout(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0,
     return _SimRolloutFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
 
 
+def sim_rollout_gauss_newton(params, dt, state, u, x_obs, weights=None, tick_weights=None, fext=None, f_base=(0.0, 0.0),
+                             f_mass=(0.0, 0.0), model="single", want=("cost", "g", "H")):
+    """The forward mode of sim_rollout_states in the parameters and the Gauss-Newton normal equations of an output-error fit
+    of the window, in ONE launch (include/cpmpc.h: cpmpc_sim_rollout_gn_batch).  x_obs [T, nx, B] is the recording, x_obs[t]
+    the measured state after tick t; with S = dx/dp carried over the ticks, r_t = wrap(x_obs[t] - xs[t]), W = diag(weights)
+    and om_t = tick_weights[t], a dict with the entries named in `want`,
+        "cost"    [B]          1/2 sum_t om_t r_t^T W r_t,
+        "g"       [np, B]      dcost/dp = -sum_t om_t S_t^T W r_t,
+        "H"       [np, np, B]  sum_t om_t S_t^T W S_t, exactly symmetric; the Gauss-Newton step is -H^-1 g,
+        "S_final" [nx, np, B]  d(last state)/dp,
+        "x_final" [nx, B]      the last state.
+    weights: nx numbers >= 0 or None (ones); 0 says that state was not measured (positions only: (1, 1, 0, 0)).
+    tick_weights: [T, B] or None (ones); 0 says that sample is missing.  x_obs holds finite numbers there all the same, and
+    may be None where none of cost, g, H is asked for.  S never goes to memory and no per-tick Jacobian is formed.  params
+    (np numbers or an [np, B] tensor; g and H are per problem either way), dt and the forces as sim_rollout_states'.
+    Not differentiated: the external forces, dt and the state (sim_rollout_vjp has its gradient).
+
+    Several recorded windows of one plant: lay them side by side as columns (2 B columns for two windows, the parameters
+    repeated) and add the windows' cost, g and H in torch before solving; the kernel knows nothing of it."""
+    names = ("cost", "g", "H", "S_final", "x_final")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in names for w in want):
+        raise ValueError("want must name at least one of %s" % ", ".join(repr(n) for n in names))
+    a = capi.SimRolloutGn(struct_size=C.sizeof(capi.SimRolloutGn))
+    m, nx, npar, dtp, B, T, host, _keep = _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model)
+    if x_obs is not None:
+        _require_cuda_tensor(x_obs, "x_obs", dtp, (T, nx, B))
+        a.x_obs = x_obs.data_ptr()
+    elif any(w in ("cost", "g", "H") for w in want):
+        raise ValueError("x_obs (the recorded states) is required for cost, g and H")
+    w_host = None
+    if weights is not None:
+        w_host = capi.dbl_array(weights, nx)   # read by the call itself, before it returns
+        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
+    if tick_weights is not None:
+        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
+        a.tick_w = tick_weights.data_ptr()
+    shapes = {"cost": (B,), "g": (npar, B), "H": (npar, npar, B), "S_final": (nx, npar, B), "x_final": (nx, B)}
+    res = {}
+    for name in want:
+        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
+        setattr(a, name, res[name].data_ptr())
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_rollout_gn_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                          _stream_ptr()))
+    return res
+
+
+def _cholesky_solve_lanes(Hs, gs):
+    """x = H^-1 g per lane for k x k systems given as lists of [B] tensors (Hs[j][i], i <= j, is read), solved on the
+    diagonally scaled matrix by a Cholesky factorisation written out elementwise -> (x as k tensors, pd [B] bool).  pd is
+    False where a pivot is not positive (or not a number); x is meaningless there."""
+    k = len(gs)
+    pd = torch.ones_like(gs[0], dtype=torch.bool)
+    one = torch.ones_like(gs[0])
+    s = []
+    for j in range(k):
+        pd = pd & (Hs[j][j] > 0)
+        s.append(torch.rsqrt(torch.where(Hs[j][j] > 0, Hs[j][j], one)))
+    L = [[None] * k for _ in range(k)]
+    for j in range(k):
+        d = Hs[j][j] * s[j] * s[j]
+        for q in range(j):
+            d = d - L[j][q] * L[j][q]
+        pd = pd & (d > 0)
+        L[j][j] = torch.sqrt(torch.where(d > 0, d, one))
+        for i in range(j + 1, k):
+            v = Hs[i][j] * s[i] * s[j]
+            for q in range(j):
+                v = v - L[i][q] * L[j][q]
+            L[i][j] = v / L[j][j]
+    y = []
+    for j in range(k):
+        v = gs[j] * s[j]
+        for q in range(j):
+            v = v - L[j][q] * y[q]
+        y.append(v / L[j][j])
+    x = [None] * k
+    for j in range(k - 1, -1, -1):
+        v = y[j]
+        for q in range(j + 1, k):
+            v = v - L[q][j] * x[q]
+        x[j] = v / L[j][j]
+    return [x[j] * s[j] for j in range(k)], pd
+
+
+def sim_identify(params, dt, state, u, x_obs, columns, iterations=8, damping=0.0, weights=None, tick_weights=None, fext=None,
+                 f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
+    """Identifies the parameters named by `columns` (indices into the parameter vector, k <= np of them) of B plants from a
+    recorded window each, all B in lock-step on the device: the output-error fit  min_p 1/2 sum_t om_t r_t^T W r_t  of
+    sim_rollout_gauss_newton by Gauss-Newton (damping = 0) or Levenberg-Marquardt (damping > 0).  params (np numbers or an
+    [np, B] tensor, not changed) is the starting point; the other parameters stay as given.
+
+    Per iteration one sim_rollout_gauss_newton launch at the trial parameters, then per lane the k x k sub-system of
+    `columns` solved by a Cholesky factorisation written in elementwise torch (Python loops over k, no batched-LAPACK
+    backend, no host synchronisation).  damping = 0: every step is taken.  damping > 0: the step solves
+    (H + mu diag(H)) d = -g with a per-lane mu that starts at `damping`; a lane takes its step only where its cost falls and
+    then divides mu by 10, else it stays and multiplies mu by 10 -- so a rejected step spends its iteration and one more to
+    win mu back: give a damped run about twice the iterations of an undamped one.  iterations + 1 launches in all.
+
+    Returns a dict: "params" [np, B], "cost" [B] at those parameters, "ok" [B] int32 -- 0 where the sub-block of H was not
+    positive definite or the lane's data were not finite.  Such a lane stops there and keeps the parameters it had (those
+    given, if that was at the first iteration); no other lane is affected.  weights, tick_weights and the remaining
+    arguments as sim_rollout_gauss_newton's, where several windows per plant are described too."""
+    m, nx, npar = _model_dims(model)
+    cols = [int(c) for c in columns]
+    if not cols or len(set(cols)) != len(cols) or any(c < 0 or c >= npar for c in cols):
+        raise ValueError("columns must name between 1 and %d distinct parameters in [0, %d)" % (npar, npar))
+    if not (float(damping) >= 0.0):
+        raise ValueError("damping must be >= 0")
+    dtp = state.dtype
+    _require_cuda_tensor(state, "state", dtp)
+    B = int(state.shape[-1])
+    if isinstance(params, torch.Tensor):
+        _require_cuda_tensor(params, "params", dtp, (npar, B))
+        p = params.detach().clone()
+    else:
+        p = torch.tensor(list(capi.dbl_array(params, npar)), dtype=dtp, device=state.device).reshape(npar, 1).repeat(1, B)
+
+    def evaluate(q):
+        return sim_rollout_gauss_newton(q, dt, state, u, x_obs, weights=weights, tick_weights=tick_weights, fext=fext,
+                                        f_base=f_base, f_mass=f_mass, model=model)
+
+    cur = evaluate(p)
+    live = torch.isfinite(cur["cost"])
+    mu = torch.full((B,), float(damping), dtype=dtp, device=state.device)
+    for _ in range(int(iterations)):
+        H, g = cur["H"], cur["g"]
+        Hs = [[H[cj, ci] * (1.0 + mu) if ci == cj else H[cj, ci] for ci in cols] for cj in cols]
+        delta, pd = _cholesky_solve_lanes(Hs, [g[c] for c in cols])
+        for d in delta:
+            pd = pd & torch.isfinite(d)
+        live = live & pd
+        trial = p.clone()
+        for c, d in zip(cols, delta):
+            trial[c] = torch.where(live, p[c] - d, p[c])
+        new = evaluate(trial)
+        if damping > 0.0:
+            take = live & (new["cost"] < cur["cost"])
+            mu = torch.where(take, mu * 0.1, mu * 10.0)
+        else:
+            take = live & torch.isfinite(new["cost"])
+            live = take
+        p = torch.where(take, trial, p)
+        cur = {name: torch.where(take, new[name], cur[name]) for name in ("cost", "g", "H")}
+    return {"params": p, "cost": cur["cost"], "ok": live.to(torch.int32)}
+
+
 class BatchSimulator:
     """B independent pendulum::Simulator plants (optimization/simulator.hpp:10-29)."""
 

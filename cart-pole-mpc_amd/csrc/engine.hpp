@@ -243,6 +243,10 @@ struct Engine {
   // the adjoint of that rollout in one launch: g_x0, g_u [T][B], g_p of `a` that are not null (sim_rollout_vjp_kernel)
   void (*sim_rollout_vjp)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                           const cpmpc_sim_rollout_vjp* a, hipStream_t stream);
+  // the forward mode of that rollout in the parameters and the Gauss-Newton normal equations of the window in one launch:
+  // cost, g, H, S_final, x_final of `a` that are not null (sim_rollout_gn_kernels.hpp)
+  void (*sim_rollout_gn)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                         const cpmpc_sim_rollout_gn* a, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -17,6 +17,7 @@
 #include "sim_jac_kernels.hpp"
 #include "sim_param_kernels.hpp"
 #include "sim_rollout_kernels.hpp"
+#include "sim_rollout_gn_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -621,6 +622,22 @@ static void sim_rollout_vjp_impl(int64_t B, const double* dyn_shared_host, int n
   });
 }
 
+// ---- the rollout's forward mode with the normal equations of the window, one launch (sim_rollout_gn_kernels.hpp) -------
+template <typename R, typename M>
+static void sim_rollout_gn_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                                const cpmpc_sim_rollout_gn* a, hipStream_t stream) {
+  StateWeights<R, M::NX> sw;
+  for (int q = 0; q < M::NX; ++q) sw.w[q] = a->w_host ? (R)a->w_host[q] : R(1);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    const SharedPlantParams<R, M> sp = shared_plant_params<R, M, PL>(dyn_shared_host);
+    hipLaunchKernelGGL((sim_rollout_gn_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B, sp.k, sp.raw, (const R*)a->dyn,
+                       ext_from_host<R>(a->fext_host), (const R*)a->fext, n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u,
+                       (const R*)a->x_obs, sw, (const R*)a->tick_w, (R*)a->cost, (R*)a->g, (R*)a->H, (R*)a->S_final,
+                       (R*)a->x_final);
+  });
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
 // linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
@@ -757,6 +774,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
                              &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
                              &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>, &sim_dyn_impl<R, M>,           \
-                             &sim_param_jac_impl<R, M>,   &sim_rollout_impl<R, M>,     &sim_rollout_vjp_impl<R, M>};  \
+                             &sim_param_jac_impl<R, M>,   &sim_rollout_impl<R, M>,     &sim_rollout_vjp_impl<R, M>,   \
+                             &sim_rollout_gn_impl<R, M>};                                                            \
     return &e;                                                                                                       \
   }

@@ -545,6 +545,45 @@ typedef struct cpmpc_sim_rollout_vjp {
 int cpmpc_sim_rollout_vjp_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                 const cpmpc_sim_rollout_vjp* a, void* stream);
 
+/* The FORWARD mode of that rollout in the parameters, and the Gauss-Newton normal equations of an output-error fit of the
+ * window to a recording x_obs [T][NX][B] (x_obs[t] is the recorded x_{t+1}), in one launch.  With S_t = dx_t/dp, S_0 = 0,
+ *     S_{t+1} = A_t S_t + P_t                        (A_t, P_t the tick's, as cpmpc_sim_step_jac_batch / ..._param_jac_batch)
+ *     r_t     = wrap(x_obs[t] - x_{t+1}),   om_t = tick_w ? tick_w[t] : 1,   W = diag(w_host), ones where w_host is NULL
+ *     cost [B]        = 1/2 sum_t om_t r_t^T W r_t
+ *     g    [NP][B]    = -sum_t om_t S_{t+1}^T W r_t
+ *     H    [NP*NP][B] =  sum_t om_t S_{t+1}^T W S_{t+1}     (full and exactly symmetric: field j*NP + k)
+ *     S_final [NX*NP][B] = dx_T/dp, element (r, j) at field r*NP + j as P;   x_final [NX][B] = x_T.
+ * SIGN CONVENTION: g = dcost/dp, H is the Gauss-Newton approximation of d2cost/dp2, and the Gauss-Newton step is -H^-1 g.
+ * No A_t is formed and S never goes to memory: the tick's tangent propagation starts from the tangents the last tick left.
+ * A weight of 0 in w_host says that state was not measured, a tick weight of 0 that the sample is missing; x_obs must still
+ * hold finite numbers there.  x_obs is required where cost, g or H is asked for, and not read otherwise.  Every output is
+ * nullable, only those given are computed, at least one must be given, and each is bitwise the same whichever others are
+ * asked for.  dt = 0: S_final = 0, H = 0, g = 0, x_final = x0 and cost is the weighted residual of x0 against every
+ * x_obs[t].  No output may overlap x0, u, fext, dyn, x_obs or tick_w.  What is NOT differentiated: the external forces, dt
+ * and x0 (its gradient is cpmpc_sim_rollout_vjp_batch's g_x0); the wrap of the pole angles has unit derivative.  A problem
+ * with non-finite data has non-finite outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size, a negative or non-finite w_host entry and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before
+ * any device is needed. */
+typedef struct cpmpc_sim_rollout_gn {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_rollout_gn) */
+  const void* x0;         /* [NX][B], read only */
+  const void* u;          /* [T][B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* x_obs;      /* [T][NX][B] the recorded x_{t+1}; required where cost, g or H is asked for */
+  const double* w_host;   /* NX residual weights >= 0, or NULL: ones (zeros = that state was not measured) */
+  const void* tick_w;     /* [T][B] per-sample weights or NULL: ones (0 = that sample is missing) */
+  void* cost;             /* [B] or NULL */
+  void* g;                /* [NP][B] or NULL */
+  void* H;                /* [NP*NP][B] or NULL */
+  void* S_final;          /* [NX*NP][B] or NULL */
+  void* x_final;          /* [NX][B] or NULL */
+} cpmpc_sim_rollout_gn;
+int cpmpc_sim_rollout_gn_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                               const cpmpc_sim_rollout_gn* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
