@@ -12,7 +12,6 @@ import torch
 
 from . import capi
 
-_TORCH_DTYPE = {capi.F32: torch.float32, capi.F64: torch.float64}
 _CAPI_DTYPE = {torch.float32: capi.F32, torch.float64: capi.F64}
 
 
@@ -20,20 +19,41 @@ def _stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _require_cuda_tensor(t, name, dtype, shape=None):
+def _require_cuda_tensor(t, name, dtype, shape=None, contiguous=True):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise TypeError("%s must be a GPU tensor" % name)
     if t.dtype != dtype:
         raise TypeError("%s must have dtype %s, got %s" % (name, dtype, t.dtype))
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise ValueError("%s must be contiguous ([field, B], batch fastest)" % name)
-    if shape is not None and tuple(t.shape) != tuple(shape):
+    if shape is not None and t.shape != shape:   # shape: a tuple (torch.Size is one)
         raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
     return t
 
 
 def _ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _want_tuple(want, names, allow_empty=False, message=None):
+    """`want` (one name or several) as a tuple, in the order given; ValueError where it names something outside `names` or,
+    unless allow_empty, nothing.  Runs before any tensor is looked at."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in names for w in want) or not (want or allow_empty):
+        raise ValueError(message or "want must name at least one of %s" % ", ".join(repr(n) for n in names))
+    return want
+
+
+def _alloc_outputs(a, want, table, dtype, device):
+    """{name: torch.empty tensor} for the names in `want`, with table[name] = (field, shape); where a struct `a` is given the
+    tensor's pointer goes into a.field, and the fields of the names not wanted stay null."""
+    res = {}
+    for name in want:
+        field, shape = table[name]
+        res[name] = torch.empty(shape, dtype=dtype, device=device)
+        if a is not None:
+            setattr(a, field, res[name].data_ptr())
+    return res
 
 
 class BatchOutputs:
@@ -120,6 +140,7 @@ class BatchOptimization:
         self.opts = opts
         self.dtype = dtype
         self.device = int(device)
+        self._dev = torch.device("cuda", self.device)
         self.max_batch = int(max_batch)
         self._h = C.c_void_p()
         info = capi.CreateInfo(struct_size=C.sizeof(capi.CreateInfo),
@@ -148,6 +169,72 @@ class BatchOptimization:
         except Exception:
             pass
 
+    # -- marshalling --------------------------------------------------------------------------
+    def _batch_of(self, x0):
+        """B of the initial states x0 [nx, B], checked."""
+        _require_cuda_tensor(x0, "x0", self.dtype)
+        shape = x0.shape
+        if len(shape) != 2 or shape[0] != self.nx:
+            raise ValueError("x0 must be [%d, B]" % self.nx)
+        return shape[1]
+
+    def _set_dyn(self, inp, B, dyn, terminal_weights):
+        """dyn (np floats, shared, or an [np, B] tensor) and terminal_weights (None or an [nx, B] tensor) checked and set on
+        `inp`, a StepInputs or a GainInputs: both name these fields alike.  What is not given is set to null, so a reused
+        struct is safe -> what the call reads, as a list: the caller holds it until the call has returned (the host array)
+        or, for an asynchronous launch, longer (step)."""
+        if isinstance(dyn, torch.Tensor):
+            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
+            inp.dyn, inp.dyn_shared_host = dyn.data_ptr(), None
+            keep = [dyn]
+        else:
+            keep = [capi.dbl_array(dyn, self.np)]
+            inp.dyn, inp.dyn_shared_host = None, C.cast(keep[0], C.POINTER(C.c_double))
+        if terminal_weights is not None:
+            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
+            inp.terminal_weights = terminal_weights.data_ptr()
+            keep.append(terminal_weights)
+        else:
+            inp.terminal_weights = None
+        return keep
+
+    def _set_set_point(self, inp, B, set_point):
+        """set_point (a float, shared, or a [B] tensor) checked and set on `inp`, a StepInputs or a WeightVjpInputs -> the
+        tensor to keep, as a list."""
+        if isinstance(set_point, torch.Tensor):
+            _require_cuda_tensor(set_point, "set_point", self.dtype, (B,))
+            inp.set_point, inp.set_point_shared = set_point.data_ptr(), 0.0
+            return [set_point]
+        inp.set_point, inp.set_point_shared = None, float(set_point)
+        return []
+
+    def _linearisation_point(self, inp, who, dyn, z, terminal_weights, B=None):
+        """The point a plan call of the method `who` linearises at, resolved and set on the GainInputs `inp`: z a [dim, B]
+        tensor, or None = the handle's previous solution with B = previous_solution_batch().  A caller that has B from
+        elsewhere (plan_weight_vjp: from x0) passes it, having checked z against it -> (B, what the caller holds until the
+        call has returned: _set_dyn)."""
+        if B is None:
+            if z is not None:
+                _require_cuda_tensor(z, "z", self.dtype)
+                if z.dim() != 2 or z.shape[0] != self.dim:
+                    raise ValueError("z must be [dim=%d, B]" % self.dim)
+                B = int(z.shape[1])
+            else:
+                B = self.previous_solution_batch()
+                if B < 1:
+                    raise ValueError("%s(z=None) needs a previous solution: step() first, or pass z" % who)
+        inp.struct_size = C.sizeof(capi.GainInputs)
+        keep = self._set_dyn(inp, B, dyn, terminal_weights)
+        inp.z = z.data_ptr() if z is not None else None
+        return B, keep
+
+    def _cotangent_rows(self, gbar, B):
+        """n_rows of a cotangent gbar [n_rows, B] on the planned controls, checked."""
+        _require_cuda_tensor(gbar, "gbar", self.dtype)
+        if gbar.dim() != 2 or gbar.shape[1] != B:
+            raise ValueError("gbar must be [n_rows, B=%d]" % B)
+        return int(gbar.shape[0])
+
     # -- Optimization::Step -------------------------------------------------------------------
     def step(self, x0, dyn, set_point=0.0, want_predicted=True, want_stats=True, want_guess=False,
              out=None, terminal_weights=None):
@@ -155,46 +242,18 @@ class BatchOptimization:
         terminal_weights: optional [nx, B] tensor of per-problem terminal weights in state order (>= 0 cost row,
         < 0 equality row; optimization.cc:236-267), overriding the four *_final_cost_weight parameters."""
         lib = capi.load()
-        dev = torch.device("cuda", self.device)
-        _require_cuda_tensor(x0, "x0", self.dtype)
-        if x0.dim() != 2 or x0.shape[0] != self.nx:
-            raise ValueError("x0 must be [%d, B]" % self.nx)
-        B = int(x0.shape[1])
+        dev = self._dev
+        B = self._batch_of(x0)
         inp = capi.StepInputs()
         inp.x0 = x0.data_ptr()
-        keep = [x0]
-        if isinstance(dyn, torch.Tensor):
-            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
-            inp.dyn = dyn.data_ptr()
-            inp.dyn_shared_host = None
-            keep.append(dyn)
-        else:
-            arr = capi.dbl_array(dyn, self.np)
-            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
-            inp.dyn = None
-            keep.append(arr)
-        if isinstance(set_point, torch.Tensor):
-            _require_cuda_tensor(set_point, "set_point", self.dtype, (B,))
-            inp.set_point = set_point.data_ptr()
-            inp.set_point_shared = 0.0
-            keep.append(set_point)
-        else:
-            inp.set_point = None
-            inp.set_point_shared = float(set_point)
-        if terminal_weights is not None:
-            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
-            inp.terminal_weights = terminal_weights.data_ptr()
-            keep.append(terminal_weights)
-        else:
-            inp.terminal_weights = None
+        keep = [x0] + self._set_dyn(inp, B, dyn, terminal_weights) + self._set_set_point(inp, B, set_point)
 
         o = out if out is not None else BatchOutputs()
 
         def reusable(t, shape, dtype):
             # a buffer handed back in `out` is written by the kernels as `dtype` on `dev`: anything else (another
             # optimizer's outputs of the other precision, another device) must be replaced, never written through
-            return (t is not None and tuple(t.shape) == tuple(shape) and t.dtype == dtype and t.device == dev
-                    and t.is_contiguous())
+            return t is not None and t.shape == shape and t.dtype == dtype and t.device == dev and t.is_contiguous()
         if not reusable(o.u, (self.N, B), self.dtype):
             o.u = torch.empty((self.N, B), dtype=self.dtype, device=dev)
         if want_predicted and not reusable(o.predicted_states, (self.N, self.nx, B), self.dtype):
@@ -245,7 +304,7 @@ class BatchOptimization:
                                                                _stream_ptr()))
 
     def get_solution(self, B):
-        z = torch.empty((self.dim, int(B)), dtype=self.dtype, device=torch.device("cuda", self.device))
+        z = torch.empty((self.dim, int(B)), dtype=self.dtype, device=self._dev)
         with torch.cuda.device(self.device):
             capi.check(capi.load().cpmpc_get_solution(self._h, int(B), _ptr(z), _stream_ptr()))
         return z
@@ -273,28 +332,10 @@ class BatchOptimization:
         (B = previous_solution_batch()), else a [dim, B] tensor; the warm start is untouched either way.  dyn: np floats
         (shared) or an [np, B] tensor; terminal_weights: optional [nx, B] tensor as in step().  want_ok: also return the
         [B] int32 tensor that is 0 for a problem whose QP is not positive definite (its rows are NaN)."""
-        dev = torch.device("cuda", self.device)
-        if z is not None:
-            _require_cuda_tensor(z, "z", self.dtype)
-            if z.dim() != 2 or z.shape[0] != self.dim:
-                raise ValueError("z must be [dim=%d, B]" % self.dim)
-            B = int(z.shape[1])
-        else:
-            B = self.previous_solution_batch()
-            if B < 1:
-                raise ValueError("feedback_gain(z=None) needs a previous solution: step() first, or pass z")
+        dev = self._dev
+        inp = capi.GainInputs()
+        B, _held = self._linearisation_point(inp, "feedback_gain", dyn, z, terminal_weights)   # _held: until the call is back
         n_rows = int(n_rows)
-        inp = capi.GainInputs(struct_size=C.sizeof(capi.GainInputs))
-        if isinstance(dyn, torch.Tensor):
-            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
-            inp.dyn = dyn.data_ptr()
-        else:
-            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
-            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
-        if terminal_weights is not None:
-            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
-            inp.terminal_weights = terminal_weights.data_ptr()
-        inp.z = z.data_ptr() if z is not None else None
         K = torch.empty((max(n_rows, 0), self.nx, B), dtype=self.dtype, device=dev)
         ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
         with torch.cuda.device(self.device):
@@ -311,38 +352,14 @@ class BatchOptimization:
         and "ok" [B] int32 with want_ok (0: the problem's QP is not positive definite, its outputs are NaN).  Sensitivities
         of the unclamped, undamped QP at z, not of the converged solution; arguments as feedback_gain's.  Only what is
         named is computed; plan_update() applies them to the whole plan."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(w not in ("K", "k_sp", "k_up") for w in want):
-            raise ValueError("want must name at least one of 'K', 'k_sp', 'k_up'")
-        dev = torch.device("cuda", self.device)
-        if z is not None:
-            _require_cuda_tensor(z, "z", self.dtype)
-            if z.dim() != 2 or z.shape[0] != self.dim:
-                raise ValueError("z must be [dim=%d, B]" % self.dim)
-            B = int(z.shape[1])
-        else:
-            B = self.previous_solution_batch()
-            if B < 1:
-                raise ValueError("plan_sensitivity(z=None) needs a previous solution: step() first, or pass z")
+        want = _want_tuple(want, ("K", "k_sp", "k_up"))
+        dev = self._dev
+        inp = capi.GainInputs()
+        B, _held = self._linearisation_point(inp, "plan_sensitivity", dyn, z, terminal_weights)
         n_rows = int(n_rows)
-        inp = capi.GainInputs(struct_size=C.sizeof(capi.GainInputs))
-        if isinstance(dyn, torch.Tensor):
-            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
-            inp.dyn = dyn.data_ptr()
-        else:
-            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
-            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
-        if terminal_weights is not None:
-            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
-            inp.terminal_weights = terminal_weights.data_ptr()
-        inp.z = z.data_ptr() if z is not None else None
         rows = max(n_rows, 0)
-        res = {}
-        if "K" in want:
-            res["K"] = torch.empty((rows, self.nx, B), dtype=self.dtype, device=dev)
-        for name in ("k_sp", "k_up"):
-            if name in want:
-                res[name] = torch.empty((rows, B), dtype=self.dtype, device=dev)
+        res = _alloc_outputs(None, want, {"K": (None, (rows, self.nx, B)), "k_sp": (None, (rows, B)), "k_up": (None, (rows, B))},
+                             self.dtype, dev)
         ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
         with torch.cuda.device(self.device):
             capi.check(capi.load().cpmpc_plan_sensitivity_batch(self._h, B, C.byref(inp), n_rows, _ptr(res.get("K")),
@@ -362,40 +379,13 @@ class BatchOptimization:
         and "ok" [B] int32 with want_ok (0: the problem's QP is not positive definite, its outputs are NaN).  K, k_sp and
         k_up are never formed: one linearisation and one pass over it.  Gradients of the unclamped, undamped Gauss-Newton QP
         at z, not of the converged solution; arguments as feedback_gain's.  Only what is named is computed."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or any(w not in ("x0", "set_point", "u_prev") for w in want):
-            raise ValueError("want must name at least one of 'x0', 'set_point', 'u_prev'")
-        dev = torch.device("cuda", self.device)
-        if z is not None:
-            _require_cuda_tensor(z, "z", self.dtype)
-            if z.dim() != 2 or z.shape[0] != self.dim:
-                raise ValueError("z must be [dim=%d, B]" % self.dim)
-            B = int(z.shape[1])
-        else:
-            B = self.previous_solution_batch()
-            if B < 1:
-                raise ValueError("plan_vjp(z=None) needs a previous solution: step() first, or pass z")
-        _require_cuda_tensor(gbar, "gbar", self.dtype)
-        if gbar.dim() != 2 or gbar.shape[1] != B:
-            raise ValueError("gbar must be [n_rows, B=%d]" % B)
-        n_rows = int(gbar.shape[0])
-        inp = capi.GainInputs(struct_size=C.sizeof(capi.GainInputs))
-        if isinstance(dyn, torch.Tensor):
-            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
-            inp.dyn = dyn.data_ptr()
-        else:
-            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
-            inp.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
-        if terminal_weights is not None:
-            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
-            inp.terminal_weights = terminal_weights.data_ptr()
-        inp.z = z.data_ptr() if z is not None else None
-        res = {}
-        if "x0" in want:
-            res["x0"] = torch.empty((self.nx, B), dtype=self.dtype, device=dev)
-        for name in ("set_point", "u_prev"):
-            if name in want:
-                res[name] = torch.empty((B,), dtype=self.dtype, device=dev)
+        want = _want_tuple(want, ("x0", "set_point", "u_prev"))
+        dev = self._dev
+        inp = capi.GainInputs()
+        B, _held = self._linearisation_point(inp, "plan_vjp", dyn, z, terminal_weights)
+        n_rows = self._cotangent_rows(gbar, B)
+        res = _alloc_outputs(None, want, {"x0": (None, (self.nx, B)), "set_point": (None, (B,)), "u_prev": (None, (B,))},
+                             self.dtype, dev)
         ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
         with torch.cuda.device(self.device):
             capi.check(capi.load().cpmpc_plan_vjp_batch(self._h, B, C.byref(inp), n_rows, _ptr(gbar), _ptr(res.get("x0")),
@@ -419,14 +409,10 @@ class BatchOptimization:
         depend on them.  Gradients of the unclamped, undamped Gauss-Newton QP at z, not through the line search, the clamps
         or earlier iterations; none with respect to the dynamics parameters.  dyn, z, terminal_weights as feedback_gain's.
         want may be empty when want_du is set (gbar is then only read for its shape and may be None with n_rows = N)."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if any(w not in ("terminal", "u", "du_dt") for w in want) or not (want or want_du):
-            raise ValueError("want must name some of 'terminal', 'u', 'du_dt' (or nothing, with want_du)")
-        dev = torch.device("cuda", self.device)
-        _require_cuda_tensor(x0, "x0", self.dtype)
-        if x0.dim() != 2 or x0.shape[0] != self.nx:
-            raise ValueError("x0 must be [%d, B]" % self.nx)
-        B = int(x0.shape[1])
+        want = _want_tuple(want, ("terminal", "u", "du_dt"), allow_empty=want_du,
+                           message="want must name some of 'terminal', 'u', 'du_dt' (or nothing, with want_du)")
+        dev = self._dev
+        B = self._batch_of(x0)
         if z is not None:
             _require_cuda_tensor(z, "z", self.dtype, (self.dim, B))
         elif self.previous_solution_batch() < B:
@@ -436,39 +422,17 @@ class BatchOptimization:
                 raise ValueError("gbar may be None only when du is the only output")
             n_rows = self.N
         else:
-            _require_cuda_tensor(gbar, "gbar", self.dtype)
-            if gbar.dim() != 2 or gbar.shape[1] != B:
-                raise ValueError("gbar must be [n_rows, B=%d]" % B)
-            n_rows = int(gbar.shape[0])
+            n_rows = self._cotangent_rows(gbar, B)
         inp = capi.WeightVjpInputs(struct_size=C.sizeof(capi.WeightVjpInputs))
-        inp.lin.struct_size = C.sizeof(capi.GainInputs)
-        if isinstance(dyn, torch.Tensor):
-            _require_cuda_tensor(dyn, "dyn", self.dtype, (self.np, B))
-            inp.lin.dyn = dyn.data_ptr()
-        else:
-            arr = capi.dbl_array(dyn, self.np)   # read by the call itself, before it returns
-            inp.lin.dyn_shared_host = C.cast(arr, C.POINTER(C.c_double))
-        if terminal_weights is not None:
-            _require_cuda_tensor(terminal_weights, "terminal_weights", self.dtype, (self.nx, B))
-            inp.lin.terminal_weights = terminal_weights.data_ptr()
-        inp.lin.z = z.data_ptr() if z is not None else None
+        _, _held = self._linearisation_point(inp.lin, "plan_weight_vjp", dyn, z, terminal_weights, B=B)
         inp.x0 = x0.data_ptr()
-        if isinstance(set_point, torch.Tensor):
-            _require_cuda_tensor(set_point, "set_point", self.dtype, (B,))
-            inp.set_point = set_point.data_ptr()
-        else:
-            inp.set_point_shared = float(set_point)
+        self._set_set_point(inp, B, set_point)
         if u_prev is not None:
             _require_cuda_tensor(u_prev, "u_prev", self.dtype, (B,))
             inp.u_prev = u_prev.data_ptr()
-        res = {}
-        if "terminal" in want:
-            res["terminal"] = torch.empty((self.nx, B), dtype=self.dtype, device=dev)
-        for name in ("u", "du_dt"):
-            if name in want:
-                res[name] = torch.empty((B,), dtype=self.dtype, device=dev)
-        if want_du:
-            res["du"] = torch.empty((n_rows, B), dtype=self.dtype, device=dev)
+        res = _alloc_outputs(None, want + (("du",) if want_du else ()),
+                             {"terminal": (None, (self.nx, B)), "u": (None, (B,)), "du_dt": (None, (B,)),
+                              "du": (None, (n_rows, B))}, self.dtype, dev)
         ok = torch.empty((B,), dtype=torch.int32, device=dev) if want_ok else None
         with torch.cuda.device(self.device):
             capi.check(capi.load().cpmpc_plan_weight_vjp_batch(self._h, B, C.byref(inp), n_rows, _ptr(gbar),
@@ -506,12 +470,9 @@ class BatchOptimization:
             raise ValueError("weight_grad=True needs a terminal_weights tensor")
         u_prev = None
         if weight_grad:   # what prepare_kernel reads before the previous solution is overwritten (optimization.cc:288-291)
-            _require_cuda_tensor(x0, "x0", self.dtype)
-            if x0.dim() != 2 or x0.shape[0] != self.nx:
-                raise ValueError("x0 must be [%d, B]" % self.nx)
-            B = int(x0.shape[1])
+            B = self._batch_of(x0)
             warm = min(self.previous_solution_batch(), B)
-            u_prev = torch.zeros((B,), dtype=self.dtype, device=torch.device("cuda", self.device))
+            u_prev = torch.zeros((B,), dtype=self.dtype, device=self._dev)
             if warm > 0:   # (the C-ABI reads a solution whole: one [dim, warm] copy, of which row nx S is control 0)
                 u_prev[:warm] = self.get_solution(warm)[self.nx * self.S]
         o = self.step(x0, dyn, set_point, terminal_weights=terminal_weights, **step_kw)
@@ -578,31 +539,46 @@ class BatchOptimization:
         return res
 
 
+def _needing_grad(ctx, inputs, names):
+    """Those of `names` that need a gradient, each looked up at its own position among the forward's `inputs`."""
+    return [n for n in names if ctx.needs_input_grad[inputs.index(n)]]
+
+
+def _masked_plan_vjp(ctx, gbar, want):
+    """One plan_vjp call at what the forward kept on ctx, for the inputs in `want` (none: no call); a problem whose QP is
+    not positive definite (ok = 0) gets gradient 0, not NaN -> {name: gradient}."""
+    if not want:
+        return {}
+    res = ctx.opt.plan_vjp(ctx.dyn, gbar, z=ctx.z, terminal_weights=ctx.terminal_weights, want=want, want_ok=True)
+    live = res["ok"] != 0
+    return {name: torch.where(live, res[name], torch.zeros_like(res[name])) for name in want}
+
+
 class _PlanVjpFunction(torch.autograd.Function):
     """u[:n_rows] of a finished step as a function of x0 and the [B] set-point: backward is one plan_vjp call at the step's
     own solution (BatchOptimization.step_differentiable)."""
 
+    INPUTS = ("opt", "u_all", "n_rows", "z", "dyn", "tw_kept", "x0", "set_point")   # forward's, in its order
+
     @staticmethod
-    def forward(ctx, opt, u_all, n_rows, z, dyn, terminal_weights, x0, set_point):
-        ctx.opt, ctx.z, ctx.dyn, ctx.terminal_weights = opt, z, dyn, terminal_weights
+    def forward(ctx, opt, u_all, n_rows, z, dyn, tw_kept, x0, set_point):
+        ctx.opt, ctx.z, ctx.dyn, ctx.terminal_weights = opt, z, dyn, tw_kept
         return u_all[:n_rows].clone()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gbar):
-        want = [name for name, i in (("x0", 6), ("set_point", 7)) if ctx.needs_input_grad[i]]
-        grads = {}
-        if want:
-            res = ctx.opt.plan_vjp(ctx.dyn, gbar.contiguous(), z=ctx.z, terminal_weights=ctx.terminal_weights, want=want,
-                                   want_ok=True)
-            live = res["ok"] != 0
-            grads = {name: torch.where(live, res[name], torch.zeros_like(res[name])) for name in want}
-        return None, None, None, None, None, None, grads.get("x0"), grads.get("set_point")
+        inputs = _PlanVjpFunction.INPUTS
+        grads = _masked_plan_vjp(ctx, gbar.contiguous(), _needing_grad(ctx, inputs, ("x0", "set_point")))
+        return tuple(grads.get(name) for name in inputs)
 
 
 class _PlanWeightVjpFunction(torch.autograd.Function):
     """_PlanVjpFunction with terminal_weights as a third differentiable input: backward adds one plan_weight_vjp call at the
     step's z, x0, set-point and u_prev (BatchOptimization.step_differentiable(weight_grad=True))."""
+
+    INPUTS = ("opt", "u_all", "n_rows", "z", "dyn", "tw_kept", "x0_kept", "sp_kept", "u_prev", "x0", "set_point",
+              "terminal_weights")   # forward's, in its order
 
     @staticmethod
     def forward(ctx, opt, u_all, n_rows, z, dyn, tw_kept, x0_kept, sp_kept, u_prev, x0, set_point, terminal_weights):
@@ -613,19 +589,14 @@ class _PlanWeightVjpFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gbar):
+        inputs = _PlanWeightVjpFunction.INPUTS
         gbar = gbar.contiguous()
-        want = [name for name, i in (("x0", 9), ("set_point", 10)) if ctx.needs_input_grad[i]]
-        grads = {}
-        if want:
-            res = ctx.opt.plan_vjp(ctx.dyn, gbar, z=ctx.z, terminal_weights=ctx.terminal_weights, want=want, want_ok=True)
-            live = res["ok"] != 0
-            grads = {name: torch.where(live, res[name], torch.zeros_like(res[name])) for name in want}
-        g_tw = None
-        if ctx.needs_input_grad[11]:
+        grads = _masked_plan_vjp(ctx, gbar, _needing_grad(ctx, inputs, ("x0", "set_point")))
+        if _needing_grad(ctx, inputs, ("terminal_weights",)):
             res = ctx.opt.plan_weight_vjp(ctx.x0, ctx.dyn, gbar, set_point=ctx.set_point, u_prev=ctx.u_prev, z=ctx.z,
                                           terminal_weights=ctx.terminal_weights, want=("terminal",), want_ok=True)
-            g_tw = torch.where(res["ok"] != 0, res["terminal"], torch.zeros_like(res["terminal"]))
-        return None, None, None, None, None, None, None, None, None, grads.get("x0"), grads.get("set_point"), g_tw
+            grads["terminal_weights"] = torch.where(res["ok"] != 0, res["terminal"], torch.zeros_like(res["terminal"]))
+        return tuple(grads.get(name) for name in inputs)
 
 
 def _fext(fext):
@@ -739,30 +710,57 @@ def plan_update(u_nom, K=None, x_nom=None, x=None, k_sp=None, sp_nom=None, sp=No
     return out
 
 
-def _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, names):
-    """One cpmpc_sim_step_jac_batch call on the current stream for the outputs in `names` (fields of cpmpc_sim_jac)."""
-    m, nx, npar = _model_dims(model)
+def _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a=None, ticks=False):
+    """What every plant call reads, checked: state [nx, B]; u [B], or with `ticks` [T, B], T >= 1; fext None or [4, B];
+    params np floats or an [np, B] tensor (None: the caller marshals them itself), for dims = _model_dims(model).  Where a
+    struct `a` is given they are set on it: the step structs call the state `state`, the rollout structs `x0`.
+    -> (B, T, host params or None, device pointer of the params or None, the shared forces as the host array that the call
+    reads before it returns: the caller holds it, and the host params, until then)."""
+    _, nx, npar = dims
     dtp = state.dtype
     _require_cuda_tensor(state, "state", dtp)
-    if state.dim() != 2 or state.shape[0] != nx:
+    shape = state.shape
+    if len(shape) != 2 or shape[0] != nx:
         raise ValueError("state must be [%d, B]" % nx)
-    B = int(state.shape[1])
-    _require_cuda_tensor(u, "u", dtp, (B,))
-    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)   # read by the call itself, before it returns
-    a = capi.SimJac(struct_size=C.sizeof(capi.SimJac))
-    a.state, a.u = state.data_ptr(), u.data_ptr()
-    a.fext_host = C.cast(shared, C.POINTER(C.c_double))
+    B, T = shape[1], 1
+    if ticks:
+        _require_cuda_tensor(u, "u", dtp)
+        if u.dim() != 2 or u.shape[0] < 1 or u.shape[1] != B:
+            raise ValueError("u must be [T, B] with T >= 1")
+        T = u.shape[0]
+    else:
+        _require_cuda_tensor(u, "u", dtp, (B,))
     if fext is not None:
         _require_cuda_tensor(fext, "fext", dtp, (4, B))
-        a.fext = fext.data_ptr()
+    host = dev = None
+    if isinstance(params, torch.Tensor):
+        _require_cuda_tensor(params, "params", dtp, (npar, B))
+        dev = params.data_ptr()
+    elif params is not None:
+        host = capi.dbl_array(params, npar)
+    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
+    if a is not None:
+        setattr(a, "x0" if ticks else "state", state.data_ptr())
+        a.u = u.data_ptr()
+        a.fext_host = C.cast(shared, C.POINTER(C.c_double))
+        if fext is not None:
+            a.fext = fext.data_ptr()
+        if dev is not None:
+            a.dyn = dev
+    return B, T, host, dev, shared
+
+
+def _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, names):
+    """One cpmpc_sim_step_jac_batch call on the current stream for the outputs in `names` (fields of cpmpc_sim_jac)."""
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimJac(struct_size=C.sizeof(capi.SimJac))
+    B, _, _, _, _held = _plant_inputs(dims, state, u, None, fext, f_base, f_mass, a)   # the call takes shared params only
     if gbar is not None:
         _require_cuda_tensor(gbar, "gbar", dtp, (nx, B))
         a.gbar = gbar.data_ptr()
-    shapes = {"x_new": (nx, B), "A": (nx, nx, B), "Bu": (nx, B), "gx": (nx, B), "gu": (B,)}
-    res = {}
-    for name in names:
-        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
-        setattr(a, name, res[name].data_ptr())
+    res = _alloc_outputs(a, names, {"x_new": ("x_new", (nx, B)), "A": ("A", (nx, nx, B)), "Bu": ("Bu", (nx, B)),
+                                    "gx": ("gx", (nx, B)), "gu": ("gu", (B,))}, dtp, state.device)
     with torch.cuda.device(state.device):
         capi.check(capi.load().cpmpc_sim_step_jac_batch(m, _CAPI_DTYPE[dtp], B, capi.dbl_array(params, npar), float(dt),
                                                         C.byref(a), _stream_ptr()))
@@ -779,9 +777,7 @@ def sim_step_jacobian(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass
     the product of the sub-steps' RK4 Jacobians.  params, dt, f_base / f_mass / fext as BatchSimulator.step's.  Not
     differentiated here: the dynamics parameters (sim_step_param_jacobian does that), the external forces and dt.  Only
     what is named is computed."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("x_new", "A", "Bu") for w in want):
-        raise ValueError("want must name at least one of 'x_new', 'A', 'Bu'")
+    want = _want_tuple(want, ("x_new", "A", "Bu"))
     return _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, None, want)
 
 
@@ -793,62 +789,37 @@ def sim_step_vjp(params, dt, state, u, gbar, fext=None, f_base=(0.0, 0.0), f_mas
         "u" [B]      Bu . gbar.
     A and Bu are contracted in registers and never written to memory: one kernel.  Not differentiated here: the dynamics
     parameters (sim_step_param_vjp does that), the external forces and dt.  Other arguments as sim_step_jacobian's."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("x", "u") for w in want):
-        raise ValueError("want must name at least one of 'x', 'u'")
+    want = _want_tuple(want, ("x", "u"))
     res = _sim_jac_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, ["g" + w for w in want])
     return {w: res["g" + w] for w in want}
 
 
-def _dyn_arg(params, npar, dtp, B):
-    """-> (shared host array or None, device pointer or None) of a parameter set given as npar floats or as an [npar, B] tensor."""
-    if isinstance(params, torch.Tensor):
-        _require_cuda_tensor(params, "params", dtp, (npar, B))
-        return None, params.data_ptr()
-    return capi.dbl_array(params, npar), None
-
-
-def _plant_step(model, npar, dtp, B, params, dt, u, shared, fext, state):
-    """The plant step in place on `state`: npar floats -> cpmpc_sim_step_batch_model, as ever; an [npar, B] tensor ->
-    cpmpc_sim_step_dyn_batch (per-problem parameters)."""
-    if isinstance(params, torch.Tensor):
-        _require_cuda_tensor(params, "params", dtp, (npar, B))
-        capi.check(capi.load().cpmpc_sim_step_dyn_batch(model, _CAPI_DTYPE[dtp], B, None, _ptr(params), float(dt), _ptr(u),
-                                                        shared, _ptr(fext), _ptr(state), _stream_ptr()))
-    else:
-        capi.check(capi.load().cpmpc_sim_step_batch_model(model, _CAPI_DTYPE[dtp], B, capi.dbl_array(params, npar),
-                                                          float(dt), _ptr(u), shared, _ptr(fext), _ptr(state),
-                                                          _stream_ptr()))
+def _plant_step(dims, dt, state, u, params, fext, f_base, f_mass, out):
+    """The plant step from `state` under u, in place on `out` (`state` itself, or a copy of it): np floats ->
+    cpmpc_sim_step_batch_model, as ever; an [np, B] tensor -> cpmpc_sim_step_dyn_batch (per-problem parameters)."""
+    B, _, host, dev, shared = _plant_inputs(dims, state, u, params, fext, f_base, f_mass)
+    dtype = _CAPI_DTYPE[state.dtype]
+    with torch.cuda.device(state.device):
+        if dev is not None:
+            capi.check(capi.load().cpmpc_sim_step_dyn_batch(dims[0], dtype, B, None, C.c_void_p(dev), float(dt), _ptr(u),
+                                                            shared, _ptr(fext), _ptr(out), _stream_ptr()))
+        else:
+            capi.check(capi.load().cpmpc_sim_step_batch_model(dims[0], dtype, B, host, float(dt), _ptr(u), shared,
+                                                              _ptr(fext), _ptr(out), _stream_ptr()))
 
 
 def _sim_param_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, names):
     """One cpmpc_sim_step_param_jac_batch call on the current stream for the outputs in `names` (fields of
     cpmpc_sim_param_jac)."""
-    m, nx, npar = _model_dims(model)
+    m, nx, npar = dims = _model_dims(model)
     dtp = state.dtype
-    _require_cuda_tensor(state, "state", dtp)
-    if state.dim() != 2 or state.shape[0] != nx:
-        raise ValueError("state must be [%d, B]" % nx)
-    B = int(state.shape[1])
-    _require_cuda_tensor(u, "u", dtp, (B,))
-    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)   # read by the call itself, before it returns
     a = capi.SimParamJac(struct_size=C.sizeof(capi.SimParamJac))
-    a.state, a.u = state.data_ptr(), u.data_ptr()
-    a.fext_host = C.cast(shared, C.POINTER(C.c_double))
-    if fext is not None:
-        _require_cuda_tensor(fext, "fext", dtp, (4, B))
-        a.fext = fext.data_ptr()
+    B, _, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a)
     if gbar is not None:
         _require_cuda_tensor(gbar, "gbar", dtp, (nx, B))
         a.gbar = gbar.data_ptr()
-    host, dev = _dyn_arg(params, npar, dtp, B)
-    if dev is not None:
-        a.dyn = dev
-    shapes = {"x_new": (nx, B), "P": (nx, npar, B), "gp": (npar, B), "gx": (nx, B), "gu": (B,)}
-    res = {}
-    for name in names:
-        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
-        setattr(a, name, res[name].data_ptr())
+    res = _alloc_outputs(a, names, {"x_new": ("x_new", (nx, B)), "P": ("P", (nx, npar, B)), "gp": ("gp", (npar, B)),
+                                    "gx": ("gx", (nx, B)), "gu": ("gu", (B,))}, dtp, state.device)
     with torch.cuda.device(state.device):
         capi.check(capi.load().cpmpc_sim_step_param_jac_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), C.byref(a),
                                                               _stream_ptr()))
@@ -865,9 +836,7 @@ def sim_step_param_jacobian(params, dt, state, u, fext=None, f_base=(0.0, 0.0), 
     params: np floats (one plant for all) or an [np, B] tensor (a plant per problem).  First derivatives of the accelerations
     only; the control and the external forces are held, the wrap has unit derivative.  Not differentiated: the external
     forces and dt."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("x_new", "P") for w in want):
-        raise ValueError("want must name at least one of 'x_new', 'P'")
+    want = _want_tuple(want, ("x_new", "P"))
     return _sim_param_call(params, dt, state, u, fext, f_base, f_mass, model, None, want)
 
 
@@ -879,11 +848,28 @@ def sim_step_param_vjp(params, dt, state, u, gbar, fext=None, f_base=(0.0, 0.0),
         "x" [nx, B]  A^T gbar,
         "u" [B]      Bu . gbar.
     P, A and Bu are contracted in registers and never written to memory.  params as sim_step_param_jacobian's."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("p", "x", "u") for w in want):
-        raise ValueError("want must name at least one of 'p', 'x', 'u'")
+    want = _want_tuple(want, ("p", "x", "u"))
     res = _sim_param_call(params, dt, state, u, fext, f_base, f_mass, model, gbar, ["g" + w for w in want])
     return {w: res["g" + w] for w in want}
+
+
+_PLANT_INPUTS = ("state", "u", "params", "dt", "fext", "f_base", "f_mass", "model")   # forward's, of both plant functions
+_PLANT_GRADS = {"state": "x", "u": "u", "params": "p"}   # a differentiable input -> its name in the vjp calls' `want`
+
+
+def _freeze_plant_args(ctx, params, dt, fext, f_base, f_mass, model):
+    """The forward's own copies of what its backward passes on beside (state, u): later changes by the caller do not reach
+    an earlier graph."""
+    ctx.args = (params.detach().clone() if isinstance(params, torch.Tensor) else [float(v) for v in params], float(dt),
+                None if fext is None else fext.detach().clone(), tuple(f_base), tuple(f_mass), model)
+
+
+def _plant_backward(ctx, vjp):
+    """The gradients of a plant function from one `vjp` call for those of its differentiable inputs that need one (none: no
+    call; parameters given as numbers never do), as backward's return value."""
+    want = [_PLANT_GRADS[n] for n in _needing_grad(ctx, _PLANT_INPUTS, _PLANT_GRADS)]
+    res = vjp(want) if want else {}
+    return tuple(res.get(_PLANT_GRADS.get(name)) for name in _PLANT_INPUTS)
 
 
 class _SimStepFunction(torch.autograd.Function):
@@ -893,25 +879,10 @@ class _SimStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, state, u, params, dt, fext, f_base, f_mass, model):
-        m, nx, npar = _model_dims(model)
-        dtp = state.dtype
-        _require_cuda_tensor(state, "state", dtp)
-        if state.dim() != 2 or state.shape[0] != nx:
-            raise ValueError("state must be [%d, B]" % nx)
-        B = int(state.shape[1])
-        _require_cuda_tensor(u, "u", dtp, (B,))
-        if fext is not None:
-            _require_cuda_tensor(fext, "fext", dtp, (4, B))
-        per_problem = isinstance(params, torch.Tensor)
-        if per_problem:
-            _require_cuda_tensor(params, "params", dtp, (npar, B))
-        ctx.args = (params.detach().clone() if per_problem else [float(v) for v in params], float(dt),
-                    None if fext is None else fext.detach().clone(), tuple(f_base), tuple(f_mass), model)
+        _freeze_plant_args(ctx, params, dt, fext, f_base, f_mass, model)
         ctx.save_for_backward(state.detach().clone(), u.detach().clone())
         out = state.detach().clone()
-        shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
-        with torch.cuda.device(state.device):
-            _plant_step(m, npar, dtp, B, params.detach() if per_problem else params, dt, u, shared, fext, out)
+        _plant_step(_model_dims(model), dt, state, u, params, fext, f_base, f_mass, out)
         return out
 
     @staticmethod
@@ -919,19 +890,10 @@ class _SimStepFunction(torch.autograd.Function):
     def backward(ctx, gbar):
         state, u = ctx.saved_tensors
         params, dt, fext, f_base, f_mass, model = ctx.args
-        want = [name for name, i in (("x", 0), ("u", 1)) if ctx.needs_input_grad[i]]
-        res = {}
-        if isinstance(params, torch.Tensor):   # per-problem parameters: one call for every gradient asked for
-            if ctx.needs_input_grad[2]:
-                want = ["p"] + want
-            if want:
-                res = sim_step_param_vjp(params, dt, state, u, gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass,
-                                         model=model, want=want)
-            return res.get("x"), res.get("u"), res.get("p"), None, None, None, None, None
-        if want:
-            res = sim_step_vjp(params, dt, state, u, gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass, model=model,
-                               want=want)
-        return res.get("x"), res.get("u"), None, None, None, None, None, None
+        # per-problem parameters: one sim_step_param_vjp call for every gradient asked for
+        call = sim_step_param_vjp if isinstance(params, torch.Tensor) else sim_step_vjp
+        return _plant_backward(ctx, lambda want: call(params, dt, state, u, gbar.contiguous(), fext=fext, f_base=f_base,
+                                                      f_mass=f_mass, model=model, want=want))
 
 
 def sim_step(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
@@ -948,46 +910,18 @@ def sim_step(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.
     return _SimStepFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
 
 
-def _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model):
-    """The inputs the two rollout structs share, checked and set on `a` -> (model id, nx, np, dtype, B, T, host params, keep)."""
-    m, nx, npar = _model_dims(model)
-    dtp = state.dtype
-    _require_cuda_tensor(state, "state", dtp)
-    if state.dim() != 2 or state.shape[0] != nx:
-        raise ValueError("state must be [%d, B]" % nx)
-    B = int(state.shape[1])
-    _require_cuda_tensor(u, "u", dtp)
-    if u.dim() != 2 or int(u.shape[0]) < 1 or int(u.shape[1]) != B:
-        raise ValueError("u must be [T, B] with T >= 1")
-    T = int(u.shape[0])
-    shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)   # read by the call itself, before it returns
-    a.x0, a.u = state.data_ptr(), u.data_ptr()
-    a.fext_host = C.cast(shared, C.POINTER(C.c_double))
-    if fext is not None:
-        _require_cuda_tensor(fext, "fext", dtp, (4, B))
-        a.fext = fext.data_ptr()
-    host, dev = _dyn_arg(params, npar, dtp, B)
-    if dev is not None:
-        a.dyn = dev
-    return m, nx, npar, dtp, B, T, host, shared
-
-
 def sim_rollout_states(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single", want=("xs",)):
     """T ticks of BatchSimulator.step in ONE launch (include/cpmpc.h: cpmpc_sim_rollout_batch): from state [nx, B] (read, not
     changed) under the controls u [T, B], u[t] held over tick t, a dict with the entries named in `want`,
         "xs"      [T, nx, B]  xs[t] = the state after tick t, what t + 1 step() calls leave,
         "x_final" [nx, B]     the state after the last tick.
     params, dt, f_base / f_mass / fext as BatchSimulator.step's, the same for every tick.  No autograd: sim_rollout has it."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("xs", "x_final") for w in want):
-        raise ValueError("want must name at least one of 'xs', 'x_final'")
+    want = _want_tuple(want, ("xs", "x_final"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
     a = capi.SimRollout(struct_size=C.sizeof(capi.SimRollout))
-    m, nx, npar, dtp, B, T, host, _keep = _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model)
-    shapes = {"xs": (T, nx, B), "x_final": (nx, B)}
-    res = {}
-    for name in want:
-        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
-        setattr(a, name, res[name].data_ptr())
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    res = _alloc_outputs(a, want, {"xs": ("xs", (T, nx, B)), "x_final": ("x_final", (nx, B))}, dtp, state.device)
     with torch.cuda.device(state.device):
         capi.check(capi.load().cpmpc_sim_rollout_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a), _stream_ptr()))
     return res
@@ -1004,13 +938,13 @@ def sim_rollout_vjp(params, dt, state, u, xs, gbar=None, gbar_final=None, fext=N
     xs [T, nx, B] is a sim_rollout_states call's at the same inputs (its last row is not read; None is allowed for T = 1).
     Reverse over the ticks, forward inside a tick; the tick's A, Bu and P are contracted in registers and nothing per tick
     goes to memory.  Not differentiated: the external forces and dt.  Other arguments as sim_rollout_states'."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in ("x", "u", "p") for w in want):
-        raise ValueError("want must name at least one of 'x', 'u', 'p'")
+    want = _want_tuple(want, ("x", "u", "p"))
     if gbar is None and gbar_final is None:
         raise ValueError("one of gbar, gbar_final must be given")
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
     a = capi.SimRolloutVjp(struct_size=C.sizeof(capi.SimRolloutVjp))
-    m, nx, npar, dtp, B, T, host, _keep = _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model)
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
     if xs is not None:
         _require_cuda_tensor(xs, "xs", dtp, (T, nx, B))
         a.xs = xs.data_ptr()
@@ -1022,11 +956,7 @@ def sim_rollout_vjp(params, dt, state, u, xs, gbar=None, gbar_final=None, fext=N
     if gbar_final is not None:
         _require_cuda_tensor(gbar_final, "gbar_final", dtp, (nx, B))
         a.gbar_final = gbar_final.data_ptr()
-    fields = {"x": ("g_x0", (nx, B)), "u": ("g_u", (T, B)), "p": ("g_p", (npar, B))}
-    res = {}
-    for w in want:
-        res[w] = torch.empty(fields[w][1], dtype=dtp, device=state.device)
-        setattr(a, fields[w][0], res[w].data_ptr())
+    res = _alloc_outputs(a, want, {"x": ("g_x0", (nx, B)), "u": ("g_u", (T, B)), "p": ("g_p", (npar, B))}, dtp, state.device)
     with torch.cuda.device(state.device):
         capi.check(capi.load().cpmpc_sim_rollout_vjp_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
                                                            _stream_ptr()))
@@ -1039,9 +969,7 @@ class _SimRolloutFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, state, u, params, dt, fext, f_base, f_mass, model):
-        per_problem = isinstance(params, torch.Tensor)
-        ctx.args = (params.detach().clone() if per_problem else [float(v) for v in params], float(dt),
-                    None if fext is None else fext.detach().clone(), tuple(f_base), tuple(f_mass), model)
+        _freeze_plant_args(ctx, params, dt, fext, f_base, f_mass, model)
         x0, uu = state.detach().clone(), u.detach().clone()
         xs = sim_rollout_states(ctx.args[0], dt, x0, uu, fext=fext, f_base=f_base, f_mass=f_mass, model=model)["xs"]
         ctx.save_for_backward(x0, uu, xs)
@@ -1052,14 +980,8 @@ class _SimRolloutFunction(torch.autograd.Function):
     def backward(ctx, gbar):
         state, u, xs = ctx.saved_tensors
         params, dt, fext, f_base, f_mass, model = ctx.args
-        want = [name for name, i in (("x", 0), ("u", 1)) if ctx.needs_input_grad[i]]
-        if isinstance(params, torch.Tensor) and ctx.needs_input_grad[2]:
-            want.append("p")
-        res = {}
-        if want:
-            res = sim_rollout_vjp(params, dt, state, u, xs, gbar=gbar.contiguous(), fext=fext, f_base=f_base, f_mass=f_mass,
-                                  model=model, want=want)
-        return res.get("x"), res.get("u"), res.get("p"), None, None, None, None, None
+        return _plant_backward(ctx, lambda want: sim_rollout_vjp(params, dt, state, u, xs, gbar=gbar.contiguous(), fext=fext,
+                                                                 f_base=f_base, f_mass=f_mass, model=model, want=want))
 
 
 def sim_rollout(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
@@ -1096,12 +1018,11 @@ def sim_rollout_gauss_newton(params, dt, state, u, x_obs, weights=None, tick_wei
 
     Several recorded windows of one plant: lay them side by side as columns (2 B columns for two windows, the parameters
     repeated) and add the windows' cost, g and H in torch before solving; the kernel knows nothing of it."""
-    names = ("cost", "g", "H", "S_final", "x_final")
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in names for w in want):
-        raise ValueError("want must name at least one of %s" % ", ".join(repr(n) for n in names))
+    want = _want_tuple(want, ("cost", "g", "H", "S_final", "x_final"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
     a = capi.SimRolloutGn(struct_size=C.sizeof(capi.SimRolloutGn))
-    m, nx, npar, dtp, B, T, host, _keep = _rollout_inputs(a, params, state, u, fext, f_base, f_mass, model)
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
     if x_obs is not None:
         _require_cuda_tensor(x_obs, "x_obs", dtp, (T, nx, B))
         a.x_obs = x_obs.data_ptr()
@@ -1114,11 +1035,8 @@ def sim_rollout_gauss_newton(params, dt, state, u, x_obs, weights=None, tick_wei
     if tick_weights is not None:
         _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
         a.tick_w = tick_weights.data_ptr()
-    shapes = {"cost": (B,), "g": (npar, B), "H": (npar, npar, B), "S_final": (nx, npar, B), "x_final": (nx, B)}
-    res = {}
-    for name in want:
-        res[name] = torch.empty(shapes[name], dtype=dtp, device=state.device)
-        setattr(a, name, res[name].data_ptr())
+    res = _alloc_outputs(a, want, {"cost": ("cost", (B,)), "g": ("g", (npar, B)), "H": ("H", (npar, npar, B)),
+                                   "S_final": ("S_final", (nx, npar, B)), "x_final": ("x_final", (nx, B))}, dtp, state.device)
     with torch.cuda.device(state.device):
         capi.check(capi.load().cpmpc_sim_rollout_gn_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
                                                           _stream_ptr()))
@@ -1229,7 +1147,7 @@ class BatchSimulator:
     """B independent pendulum::Simulator plants (optimization/simulator.hpp:10-29)."""
 
     def __init__(self, batch, dtype=torch.float32, device=None, model="single"):
-        self.model, self.nx, self.np = _model_dims(model)
+        self.model, self.nx, self.np = self._dims = _model_dims(model)
         if device is None:
             device = torch.cuda.current_device()
         self.device = torch.device("cuda", int(device))
@@ -1241,22 +1159,27 @@ class BatchSimulator:
     def get_state(self):
         return self.state
 
-    def set_state(self, state):
-        _require_cuda_tensor(state, "state", self.dtype, tuple(self.state.shape))
-        self.state = state.clone()
+    def set_state(self, state, stream=None):
+        """The plants' state becomes a copy of state [nx, B].  stream None: the copy is queued on the current stream.  With a
+        torch.cuda.Stream the copy (contiguous; `state` may then be a strided view, a column range) is queued on, and
+        belongs to the pool of, that stream, and both `state` and the replaced tensor are recorded on it: the caller's
+        allocator hands neither out while that stream may still read it.  Making that stream wait for whatever produced
+        `state` is the caller's part (ClosedLoop.set_state)."""
+        _require_cuda_tensor(state, "state", self.dtype, tuple(self.state.shape), contiguous=stream is None)
+        if stream is None:
+            self.state = state.clone()
+            return
+        old = self.state
+        with torch.cuda.stream(stream):
+            self.state = state.clone(memory_format=torch.contiguous_format)
+        state.record_stream(stream)   # `state` is read there: its memory is not reused before that copy
+        old.record_stream(stream)     # the plant of the last tick may still be reading the replaced tensor
 
     def step(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """u: [B] tensor.  f_base/f_mass shared (x, y) pairs, or fext a [4, B] tensor
         {f_base.x, f_base.y, f_mass.x, f_mass.y}.  params: np floats (one plant for all), or an [np, B] tensor: a plant
         per problem (cpmpc_sim_step_dyn_batch)."""
-        B = int(self.state.shape[1])
-        _require_cuda_tensor(u, "u", self.dtype, (B,))
-        shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
-        if fext is not None:
-            _require_cuda_tensor(fext, "fext", self.dtype, (4, B))
-        with torch.cuda.device(self.device):
-            _plant_step(self.model, self.np, self.dtype, B, params.detach() if isinstance(params, torch.Tensor) else params,
-                        dt, u, shared, fext, self.state)
+        _plant_step(self._dims, dt, self.state, u, params, fext, f_base, f_mass, self.state)
 
     def step_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """step() with a backward: the state after the step is sim_step(params, dt, self.state, u, ...) -- bitwise what
@@ -1331,7 +1254,10 @@ class ClosedLoop:
         """state: [nx, B] tensor, columns in the caller's order.  May be called at any tick (a disturbance, a reset): with
         several ranges the copy is made ON each range's stream after that stream has waited for the caller's, so neither the
         range's solver / plant can read the new state before it has landed nor the caller's allocator hand the old one out
-        while the range's plant is still reading it."""
+        while the range's plant is still reading it (BatchSimulator.set_state(stream=...)).  The whole tensor is
+        checked before anything is touched -- a GPU tensor of the loop's dtype, exactly [nx, B] -- so a refused call leaves
+        every range as it was."""
+        _require_cuda_tensor(state, "state", self.dtype, (self.sims[0].nx, self.batch), contiguous=False)
         cur = torch.cuda.current_stream(self.device)
         for i, s in enumerate(self.sims):
             part = state[:, self.bounds[i]:self.bounds[i + 1]]
@@ -1340,16 +1266,7 @@ class ClosedLoop:
                 s.set_state(part.contiguous())
                 continue
             st.wait_stream(cur)                      # whatever produced `state` on the caller's stream comes first
-            old = s.state
-            _require_cuda_tensor(state, "state", self.dtype)
-            if tuple(part.shape) != tuple(old.shape):
-                raise ValueError("state must be [%d, %d]" % (old.shape[0], self.batch))
-            with torch.cuda.stream(st):
-                # the copy (contiguous: a column range of `state` is a strided view) is queued on, and belongs to the pool
-                # of, the range's stream
-                s.state = part.clone(memory_format=torch.contiguous_format)
-            part.record_stream(st)                   # `state` is read there: its memory is not reused before that copy
-            old.record_stream(st)                    # the plant of the last tick may still be reading the replaced tensor
+            s.set_state(part, stream=st)
         self._inputs_dirty = len(self.sims) > 1
 
     def _on(self, i):

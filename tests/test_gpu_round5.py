@@ -219,6 +219,9 @@ def test_set_state_and_new_set_points_mid_run_with_column_ranges(pkg, dtype):
                 for _ in range(200):
                     kick[3] += 0.002
                 kick[1] -= 0.05
+                if k == 15:   # a state one column too wide is refused whole; what follows shows that it left nothing behind
+                    with pytest.raises(ValueError):
+                        loop.set_state(torch.cat([kick, kick[:, :1]], dim=1))
                 loop.set_state(kick)
                 del kick
         if k >= 10:
@@ -238,6 +241,67 @@ def test_set_state_and_new_set_points_mid_run_with_column_ranges(pkg, dtype):
         loops[1].tick(torch.zeros((9, B), dtype=dtype, device=x0.device), 0.0)
     for loop in loops:
         loop.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_set_state_checks_the_whole_state_before_it_touches_a_range(pkg, dtype):
+    """ClosedLoop.set_state() validates once, before anything is touched: after one tick a [4, B + 1] tensor (until now
+    accepted, its last column dropped), a [4, B - 1] tensor (until now refused only after the first ranges had been
+    replaced), a tensor of the other dtype and a CPU tensor are each refused, and state() is bitwise what it was -- with
+    one range and with three (B = 130: 43 / 43 / 44 columns).  The valid call that follows, and two ticks, give the same
+    bits in both."""
+    rng = np.random.default_rng(33)
+    B = 130
+    xs = np.stack([rng.uniform(-0.3, 0.3, B), np.pi / 2 + rng.uniform(-0.4, 0.4, B), rng.uniform(-0.5, 0.5, B), rng.uniform(-1, 1, B)])
+    loops = [pkg.ClosedLoop(pkg.default_params(), B, dtype=dtype, device=0, ranges=n) for n in (1, 3)]
+    assert loops[1].bounds == [0, 43, 86, 130]
+    other = torch.float32 if dtype == torch.float64 else torch.float64
+    x1 = T(xs, dtype)
+    x2 = T(xs[:, ::-1], dtype)
+    wide, narrow = torch.cat([x2, x2[:, :1]], dim=1), x2[:, :B - 1].contiguous()
+    assert tuple(wide.shape) == (4, 131) and tuple(narrow.shape) == (4, 129)
+    for loop in loops:
+        loop.set_state(x1)
+        loop.tick(DYN_UI, 0.0)
+        before = loop.state().clone()
+        for bad, exc in ((wide, ValueError), (narrow, ValueError), (x2.to(other), TypeError), (x2.cpu(), TypeError)):
+            with pytest.raises(exc):
+                loop.set_state(bad)
+            assert torch.equal(loop.state(), before), (tuple(bad.shape), bad.dtype, bad.device)
+        loop.set_state(x2)
+        assert torch.equal(loop.state(), x2)
+        for _ in range(2):
+            loop.tick(DYN_UI, 0.0)
+    one, three = loops
+    assert torch.equal(one.state(), three.state()) and torch.equal(one.controls(), three.controls())
+    assert not torch.equal(one.state(), x2)
+    for loop in loops:
+        loop.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_simulator_set_state_on_a_side_stream_is_set_state_on_the_current_one(pkg, dtype):
+    """BatchSimulator.set_state(x, stream=s) and a step on s leave bitwise what set_state(x) and a step on the current
+    stream leave (B = 65: more than one wave, not a multiple of it)."""
+    rng = np.random.default_rng(34)
+    B = 65
+    x = T(random_states(rng, B), dtype)
+    u = T(rng.uniform(-50, 50, B), dtype)
+    here = pkg.BatchSimulator(B, dtype=dtype, device=0)
+    here.set_state(x)
+    here.step(DYN_UI, 0.01, u)
+    there = pkg.BatchSimulator(B, dtype=dtype, device=0)
+    side = torch.cuda.Stream(device=x.device)
+    side.wait_stream(torch.cuda.current_stream(x.device))   # x, u and the simulator's initial state were written here
+    there.set_state(x, stream=side)
+    with torch.cuda.stream(side):
+        there.step(DYN_UI, 0.01, u)
+    u.record_stream(side)
+    torch.cuda.current_stream(x.device).wait_stream(side)
+    assert torch.equal(there.get_state(), here.get_state())
+    assert not torch.equal(here.get_state(), x)
+    with pytest.raises(ValueError):
+        there.set_state(x[:, :B - 1], stream=side)
 
 
 def test_plain_sqp_tool_reports_both_phases_in_both_dtypes():
