@@ -20,7 +20,8 @@ def __getattr__(name):
     if name in ("BatchOptimization", "BatchSimulator", "BatchOutputs", "ClosedLoop", "dynamics_batch", "rk4_batch",
                 "feedback_apply", "plan_update", "sim_step_jacobian", "sim_step_vjp", "sim_step",
                 "sim_step_param_jacobian", "sim_step_param_vjp", "sim_rollout_states", "sim_rollout_vjp", "sim_rollout",
-                "sim_rollout_gauss_newton", "sim_identify"):
+                "sim_rollout_gauss_newton", "sim_identify", "sim_rollout_gauss_newton_x0", "sim_estimate_state",
+                "WindowEstimator"):
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

@@ -1043,10 +1043,11 @@ def sim_rollout_gauss_newton(params, dt, state, u, x_obs, weights=None, tick_wei
     return res
 
 
-def _cholesky_solve_lanes(Hs, gs):
+def _cholesky_solve_lanes(Hs, gs, pivot_floor=0.0):
     """x = H^-1 g per lane for k x k systems given as lists of [B] tensors (Hs[j][i], i <= j, is read), solved on the
     diagonally scaled matrix by a Cholesky factorisation written out elementwise -> (x as k tensors, pd [B] bool).  pd is
-    False where a pivot is not positive (or not a number); x is meaningless there."""
+    False where a pivot is not positive (or not a number); x is meaningless there.  pivot_floor: a pivot of the scaled
+    matrix (unit diagonal) at or below it counts as not positive -- what rounding leaves of an exactly singular H."""
     k = len(gs)
     pd = torch.ones_like(gs[0], dtype=torch.bool)
     one = torch.ones_like(gs[0])
@@ -1059,7 +1060,7 @@ def _cholesky_solve_lanes(Hs, gs):
         d = Hs[j][j] * s[j] * s[j]
         for q in range(j):
             d = d - L[j][q] * L[j][q]
-        pd = pd & (d > 0)
+        pd = pd & (d > pivot_floor)
         L[j][j] = torch.sqrt(torch.where(d > 0, d, one))
         for i in range(j + 1, k):
             v = Hs[i][j] * s[i] * s[j]
@@ -1118,13 +1119,24 @@ def sim_identify(params, dt, state, u, x_obs, columns, iterations=8, damping=0.0
         return sim_rollout_gauss_newton(q, dt, state, u, x_obs, weights=weights, tick_weights=tick_weights, fext=fext,
                                         f_base=f_base, f_mass=f_mass, model=model)
 
+    p, cur, live = _gauss_newton_lanes(evaluate, p, cols, iterations, damping, ("cost", "g", "H"))
+    return {"params": p, "cost": cur["cost"], "ok": live.to(torch.int32)}
+
+
+def _gauss_newton_lanes(evaluate, p, cols, iterations, damping, names, pivot_floor=0.0):
+    """The accept / reject loop of sim_identify and sim_estimate_state: B independent fits in lock-step, rows `cols` of the
+    unknowns p [n, B] moving.  evaluate(q) -> a dict with "cost" [B], "g" [n, B], "H" [n, n, B] and whatever else `names`
+    lists, at the trial point q; one call before the loop and one per iteration.  Per iteration the len(cols)-square
+    sub-system per lane through _cholesky_solve_lanes, (H + mu diag(H)) d = -g with the per-lane mu of sim_identify's
+    docstring where damping > 0.  A lane whose data are not finite or whose sub-block of H is not positive definite stops
+    and keeps what it had; pivot_floor as _cholesky_solve_lanes'.  -> (p, the entries `names` at p, live [B] bool)."""
     cur = evaluate(p)
     live = torch.isfinite(cur["cost"])
-    mu = torch.full((B,), float(damping), dtype=dtp, device=state.device)
+    mu = torch.full_like(cur["cost"], float(damping))
     for _ in range(int(iterations)):
         H, g = cur["H"], cur["g"]
         Hs = [[H[cj, ci] * (1.0 + mu) if ci == cj else H[cj, ci] for ci in cols] for cj in cols]
-        delta, pd = _cholesky_solve_lanes(Hs, [g[c] for c in cols])
+        delta, pd = _cholesky_solve_lanes(Hs, [g[c] for c in cols], pivot_floor)
         for d in delta:
             pd = pd & torch.isfinite(d)
         live = live & pd
@@ -1139,8 +1151,193 @@ def sim_identify(params, dt, state, u, x_obs, columns, iterations=8, damping=0.0
             take = live & torch.isfinite(new["cost"])
             live = take
         p = torch.where(take, trial, p)
-        cur = {name: torch.where(take, new[name], cur[name]) for name in ("cost", "g", "H")}
-    return {"params": p, "cost": cur["cost"], "ok": live.to(torch.int32)}
+        cur = {name: torch.where(take, new[name], cur[name]) for name in names}
+    return p, cur, live
+
+
+def sim_rollout_gauss_newton_x0(params, dt, state, u, x_obs, weights=None, tick_weights=None, fext=None, f_base=(0.0, 0.0),
+                                f_mass=(0.0, 0.0), model="single", want=("cost", "g", "H")):
+    """The forward mode of sim_rollout_states in the INITIAL STATE and the Gauss-Newton normal equations of an output-error
+    fit of it over the window, in ONE launch (include/cpmpc.h: cpmpc_sim_rollout_gn_x0_batch): the state-estimation half of
+    sim_rollout_gauss_newton.  x_obs [T, nx, B] is the recording, x_obs[t] the measured state after tick t; with
+    Phi_t = dxs[t]/dstate carried over the ticks, r_t = wrap(x_obs[t] - xs[t]), W = diag(weights) and om_t = tick_weights[t], a
+    dict with the entries named in `want`,
+        "cost"      [B]          1/2 sum_t om_t r_t^T W r_t,
+        "g"         [nx, B]      dcost/dstate = -sum_t om_t Phi_t^T W r_t,
+        "H"         [nx, nx, B]  sum_t om_t Phi_t^T W Phi_t, exactly symmetric; the Gauss-Newton step is -H^-1 g,
+        "Phi_final" [nx, nx, B]  d(last state)/dstate, the product of the ticks' sim_step_jacobian A,
+        "x_final"   [nx, B]      the last state.
+    weights: nx numbers >= 0 or None (ones); 0 says that state was not measured (positions only: (1, 1, 0, 0)).
+    tick_weights: [T, B] or None (ones); 0 says that sample is missing.  x_obs holds finite numbers there all the same, and
+    may be None where none of cost, g, H is asked for.  Phi never goes to memory and no per-tick Jacobian is formed.  params
+    (np numbers or an [np, B] tensor), dt and the forces as sim_rollout_states'.  Not differentiated: the parameters
+    (sim_rollout_gauss_newton), the external forces and dt."""
+    want = _want_tuple(want, ("cost", "g", "H", "Phi_final", "x_final"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimRolloutGnX0(struct_size=C.sizeof(capi.SimRolloutGnX0))
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    if x_obs is not None:
+        _require_cuda_tensor(x_obs, "x_obs", dtp, (T, nx, B))
+        a.x_obs = x_obs.data_ptr()
+    elif any(w in ("cost", "g", "H") for w in want):
+        raise ValueError("x_obs (the recorded states) is required for cost, g and H")
+    w_host = None
+    if weights is not None:
+        w_host = capi.dbl_array(weights, nx)   # read by the call itself, before it returns
+        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
+    if tick_weights is not None:
+        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
+        a.tick_w = tick_weights.data_ptr()
+    res = _alloc_outputs(a, want, {"cost": ("cost", (B,)), "g": ("g", (nx, B)), "H": ("H", (nx, nx, B)),
+                                   "Phi_final": ("Phi_final", (nx, nx, B)), "x_final": ("x_final", (nx, B))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_rollout_gn_x0_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                             _stream_ptr()))
+    return res
+
+
+def _wrap_pole_angles(d, nx):
+    """d [nx, B], a difference of states: its pole angles to the nearest multiple of 2 pi, as the kernels wrap a residual"""
+    nq = nx // 2
+    if nq > 1:
+        d = d.clone()
+        d[1:nq] = d[1:nq] - 2.0 * 3.14159265358979323846 * torch.round(d[1:nq] / (2.0 * 3.14159265358979323846))
+    return d
+
+
+def sim_estimate_state(params, dt, state, u, x_obs, iterations=8, damping=0.0, weights=None, tick_weights=None, prior=None,
+                       prior_info=None, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
+    """Estimates the state at the START of a recorded window of B plants, all B in lock-step on the device: the output-error
+    fit  min_x0 1/2 sum_t om_t r_t^T W r_t (+ the arrival cost)  of sim_rollout_gauss_newton_x0 by Gauss-Newton
+    (damping = 0) or Levenberg-Marquardt (damping > 0).  `state` [nx, B] (not changed) is the starting guess of x0; u [T, B]
+    the controls that were applied and x_obs [T, nx, B] the measurements after every tick; weights says which states were
+    measured (positions only: (1, 1, 0, 0) -- the unmeasured rows of x_obs are not used but must be finite).
+
+    Per iteration one sim_rollout_gauss_newton_x0 launch at the trial x0, then the nx x nx system per lane by the Cholesky
+    factorisation of sim_identify, with its accept / reject rule and per-lane mu (the loop is the same function);
+    iterations + 1 launches in all, no host synchronisation.  Give a damped run about twice the iterations.
+
+    The arrival cost 1/2 (x0 - prior)^T Pi (x0 - prior), with prior [nx, B] and Pi = prior_info [nx, B] (a diagonal) or
+    [nx, nx, B] (symmetric), both or neither: the pole angles of the difference are wrapped, and it is added to cost, g and H
+    in torch; the kernel knows nothing of it.
+
+    Returns a dict: "x0" [nx, B] the estimate of the window's first state, "x_final" [nx, B] the state after the window's last
+    tick from there -- the estimate of the CURRENT state, which is what a controller wants (ClosedLoop.set_state) -- "cost"
+    [B], "H" [nx, nx, B] at the estimate with the prior included (its inverse is the estimate's covariance in units of the
+    measurement variance) and "ok" [B] int32 -- 0 where H was not positive definite (a pivot of the diagonally scaled H at or below
+    8 nx eps: the window does not determine x0) or the lane's data were not finite.  Such a lane keeps its guess; no other
+    lane is affected.  The remaining arguments as sim_rollout_gauss_newton_x0's."""
+    m, nx, npar = _model_dims(model)
+    if not (float(damping) >= 0.0):
+        raise ValueError("damping must be >= 0")
+    if (prior is None) != (prior_info is None):
+        raise ValueError("prior and prior_info are given together or not at all")
+    dtp = state.dtype
+    _require_cuda_tensor(state, "state", dtp)
+    if state.dim() != 2 or state.shape[0] != nx:
+        raise ValueError("state must be [%d, B]" % nx)
+    B = int(state.shape[1])
+    diag = None
+    if prior is not None:
+        _require_cuda_tensor(prior, "prior", dtp, (nx, B))
+        _require_cuda_tensor(prior_info, "prior_info", dtp)
+        if tuple(prior_info.shape) not in ((nx, B), (nx, nx, B)):
+            raise ValueError("prior_info must be [%d, B] or [%d, %d, B]" % (nx, nx, nx))
+        diag = prior_info.dim() == 2
+        info = torch.diag_embed(prior_info.t()).permute(1, 2, 0).contiguous() if diag else prior_info
+
+    def evaluate(q):
+        res = sim_rollout_gauss_newton_x0(params, dt, q, u, x_obs, weights=weights, tick_weights=tick_weights, fext=fext,
+                                          f_base=f_base, f_mass=f_mass, model=model, want=("cost", "g", "H", "x_final"))
+        if prior is not None:
+            d = _wrap_pole_angles(q - prior, nx)
+            pd = prior_info * d if diag else torch.einsum("jkb,kb->jb", prior_info, d)
+            res["cost"] = res["cost"] + 0.5 * (d * pd).sum(dim=0)
+            res["g"] = res["g"] + pd
+            res["H"] = res["H"] + info
+        return res
+
+    # an unobservable window (one tick of positions only) has an exactly singular H, of which rounding leaves pivots of
+    # either sign at the size of 1 ulp of the scaled matrix's unit diagonal: those count as not positive
+    x0, cur, live = _gauss_newton_lanes(evaluate, state.detach().clone(), list(range(nx)), iterations, damping,
+                                        ("cost", "g", "H", "x_final"), pivot_floor=8 * nx * torch.finfo(dtp).eps)
+    return {"x0": x0, "x_final": cur["x_final"], "cost": cur["cost"], "H": cur["H"], "ok": live.to(torch.int32)}
+
+
+class WindowEstimator:
+    """A moving-horizon state estimator for B plants: the last T controls and measurements on the device, and
+    sim_estimate_state over them.  Per tick the caller push()es the control it applied and what it then measured, and
+    estimate() returns the current state [nx, B] -- what ClosedLoop.set_state() takes.
+
+    The fit's unknown is the state at the START of the window.  It is warm-started from the previous estimate, advanced by
+    one plant tick (one sim_rollout_states launch) whenever a full window drops its oldest sample; before the window is
+    full the estimator fits the ticks it has.  No arrival cost is carried from window to window (a rolling prior is not
+    built); estimate() passes a caller's prior / prior_info through.  Nothing here waits for the device."""
+
+    def __init__(self, params, dt, batch, window, state=None, dtype=torch.float64, device=None, model="single", weights=None,
+                 fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0)):
+        """window: T >= 1 ticks.  state [nx, B]: the first guess of the state before the first pushed tick (default: the
+        plants hanging at rest, BatchSimulator's initial state).  params, dt, the forces and weights are those of every
+        sim_estimate_state call."""
+        self.model = model
+        _, self.nx, self.np = _model_dims(model)
+        if device is None:
+            device = torch.cuda.current_device()
+        self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
+        self.dtype, self.batch, self.window = dtype, int(batch), int(window)
+        if self.window < 1:
+            raise ValueError("window must be >= 1")
+        self.params, self.dt, self.weights = params, float(dt), weights
+        self.forces = dict(fext=fext, f_base=f_base, f_mass=f_mass)
+        if state is None:
+            state = BatchSimulator(self.batch, dtype=dtype, device=self.device.index, model=model).get_state()
+        _require_cuda_tensor(state, "state", dtype, (self.nx, self.batch))
+        self.x0 = state.detach().clone()          # the guess of the state at the start of the window
+        self.u = torch.zeros((self.window, self.batch), dtype=dtype, device=self.device)
+        self.y = torch.zeros((self.window, self.nx, self.batch), dtype=dtype, device=self.device)
+        self.w = torch.zeros((self.window, self.batch), dtype=dtype, device=self.device)
+        self.count = 0                            # ticks held, at most `window` (a host counter: nothing is read back)
+
+    def push(self, u, y, tick_weight=None):
+        """One more tick: u [B] the control held over it, y [nx, B] the measurement after it (the rows of states that the
+        weights leave out are not used but must be finite), tick_weight [B] or None (ones; 0: the sample is missing).  A
+        full window drops its oldest tick, and the guess of its first state moves one tick on under the dropped control."""
+        _require_cuda_tensor(u, "u", self.dtype, (self.batch,))
+        _require_cuda_tensor(y, "y", self.dtype, (self.nx, self.batch))
+        if tick_weight is not None:
+            _require_cuda_tensor(tick_weight, "tick_weight", self.dtype, (self.batch,))
+        if self.count == self.window:
+            self.x0 = sim_rollout_states(self.params, self.dt, self.x0, self.u[:1], model=self.model, want="x_final",
+                                         **self.forces)["x_final"]
+            self.u, self.y, self.w = torch.roll(self.u, -1, 0), torch.roll(self.y, -1, 0), torch.roll(self.w, -1, 0)
+            at = self.window - 1
+        else:
+            at = self.count
+            self.count += 1
+        self.u[at] = u
+        self.y[at] = y
+        if tick_weight is None:
+            self.w[at] = 1.0
+        else:
+            self.w[at] = tick_weight
+
+    def held(self):
+        """The window as estimate() hands it to sim_estimate_state: (the guess [nx, B], u [n, B], y [n, nx, B], tick weights
+        [n, B]) for the n = min(ticks pushed, window) ticks held -- views of the estimator's own tensors."""
+        if self.count == 0:
+            raise ValueError("WindowEstimator: no tick has been pushed yet")
+        n = self.count
+        return self.x0, self.u[:n], self.y[:n], self.w[:n]
+
+    def estimate(self, iterations=2, damping=0.0, prior=None, prior_info=None, want_result=False):
+        """sim_estimate_state over the ticks held, from the warm start; the estimate of the window's first state is the next
+        call's guess.  Returns the current state [nx, B]; with want_result, (that, sim_estimate_state's dict)."""
+        x0, u, y, w = self.held()
+        res = sim_estimate_state(self.params, self.dt, x0, u, y, iterations=iterations, damping=damping, weights=self.weights,
+                                 tick_weights=w, prior=prior, prior_info=prior_info, model=self.model, **self.forces)
+        self.x0 = res["x0"]
+        return (res["x_final"], res) if want_result else res["x_final"]
 
 
 class BatchSimulator:

@@ -51,6 +51,7 @@ SYMBOLS = [
     "cpmpc_sim_step_jac_batch", "cpmpc_sim_step_jac_batch_host",
     "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
     "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch", "cpmpc_sim_rollout_gn_batch",
+    "cpmpc_sim_rollout_gn_x0_batch",
 ]
 
 
@@ -309,6 +310,27 @@ class SimRolloutGn(C.Structure):
     ]
 
 
+class SimRolloutGnX0(C.Structure):
+    """cpmpc_sim_rollout_gn_x0: device pointers of cpmpc_sim_rollout_gn_x0_batch; x0, u, dyn, the recording x_obs and the
+    per-sample weights tick_w are read, w_host is NX host doubles, cost, g, H, Phi_final and x_final are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("x_obs", C.c_void_p),
+        ("w_host", C.POINTER(C.c_double)),
+        ("tick_w", C.c_void_p),
+        ("cost", C.c_void_p),
+        ("g", C.c_void_p),
+        ("H", C.c_void_p),
+        ("Phi_final", C.c_void_p),
+        ("x_final", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -442,6 +464,7 @@ def load():
     L.cpmpc_sim_rollout_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRollout), vp]
     L.cpmpc_sim_rollout_vjp_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutVjp), vp]
     L.cpmpc_sim_rollout_gn_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutGn), vp]
+    L.cpmpc_sim_rollout_gn_x0_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutGnX0), vp]
     _lib = L
     return L
 

@@ -1050,6 +1050,38 @@ extern "C" int cpmpc_sim_rollout_gn_batch(int model, int dtype, int64_t B, const
   });
 }
 
+// ---- the rollout's forward mode in the initial state and the normal equations of the fit of x0 (sim_rollout_gn_x0_kernels.hpp)
+static int check_sim_rollout_gn_x0_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                        const cpmpc_sim_rollout_gn_x0* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout_gn_x0)");
+  int rc = check_rollout_common("cpmpc_sim_rollout_gn_x0", a->struct_size, sizeof(cpmpc_sim_rollout_gn_x0), a->x0, a->u,
+                                dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->cost && !a->g && !a->H && !a->Phi_final && !a->x_final)
+    return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if ((a->cost || a->g || a->H) && !a->x_obs) return fail(CPMPC_ERR_INVALID_ARG, "cost / g / H are given without x_obs");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  if (a->w_host)
+    for (size_t q = 0; q < nx; ++q)
+      if (!(a->w_host[q] >= 0.0) || !std::isfinite(a->w_host[q]))
+        return fail(CPMPC_ERR_INVALID_ARG, "w_host[%zu] must be finite and >= 0", q);
+  const ArraySpan outs[5] = {{a->cost, 1, "cost"}, {a->g, nx, "g"}, {a->H, nx * nx, "H"}, {a->Phi_final, nx * nx, "Phi_final"},
+                             {a->x_final, nx, "x_final"}};
+  const ArraySpan ins[6] = {{a->x0, nx, "x0"},     {a->u, nt, "u"},
+                            {a->fext, 4, "fext"},  {a->dyn, np, "dyn"},
+                            {a->x_obs, nt * nx, "x_obs"}, {a->tick_w, nt, "tick_w"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_rollout_gn_x0_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                             const cpmpc_sim_rollout_gn_x0* a, void* stream) {
+  int rc = check_sim_rollout_gn_x0_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_rollout_gn_x0(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

@@ -247,6 +247,10 @@ struct Engine {
   // cost, g, H, S_final, x_final of `a` that are not null (sim_rollout_gn_kernels.hpp)
   void (*sim_rollout_gn)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                          const cpmpc_sim_rollout_gn* a, hipStream_t stream);
+  // the forward mode of that rollout in the initial state and the normal equations of the fit of x0 in one launch: cost, g,
+  // H, Phi_final, x_final of `a` that are not null (sim_rollout_gn_x0_kernels.hpp)
+  void (*sim_rollout_gn_x0)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                            const cpmpc_sim_rollout_gn_x0* a, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

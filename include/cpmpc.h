@@ -584,6 +584,47 @@ typedef struct cpmpc_sim_rollout_gn {
 int cpmpc_sim_rollout_gn_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                const cpmpc_sim_rollout_gn* a, void* stream);
 
+/* The FORWARD mode of that rollout in the INITIAL STATE, and the Gauss-Newton normal equations of an output-error fit of x0
+ * to a recording x_obs [T][NX][B] (x_obs[t] is the recorded x_{t+1}), in one launch: the state-estimation half of the call
+ * above.  With Phi_t = dx_t/dx0, Phi_0 = I,
+ *     Phi_{t+1} = A_t Phi_t                          (A_t the tick's dx_{t+1}/dx_t, as cpmpc_sim_step_jac_batch's A)
+ *     r_t     = wrap(x_obs[t] - x_{t+1}),   om_t = tick_w ? tick_w[t] : 1,   W = diag(w_host), ones where w_host is NULL
+ *     cost [B]        = 1/2 sum_t om_t r_t^T W r_t
+ *     g    [NX][B]    = -sum_t om_t Phi_{t+1}^T W r_t
+ *     H    [NX*NX][B] =  sum_t om_t Phi_{t+1}^T W Phi_{t+1} (full and exactly symmetric: field j*NX + k)
+ *     Phi_final [NX*NX][B] = dx_T/dx0, element (r, c) at field r*NX + c as A;   x_final [NX][B] = x_T.
+ * SIGN CONVENTION: g = dcost/dx0, H is the Gauss-Newton approximation of d2cost/dx0^2, and the Gauss-Newton step is
+ * -H^-1 g.  No A_t is formed and Phi never goes to memory: the tick's tangent propagation starts from the tangents the last
+ * tick left; the columns of Phi that are known in closed form are neither stored nor propagated.
+ * A weight of 0 in w_host says that state was not measured (positions only: 1, 1, 0, 0), a tick weight of 0 that the sample
+ * is missing; x_obs must still hold finite numbers there.  x_obs is required where cost, g or H is asked for, and not read
+ * otherwise.  Every output is nullable, only those given are computed, at least one must be given, and each is bitwise the
+ * same whichever others are asked for.  dt = 0: Phi_final = I, x_final = x0, H = sum_t om_t W, g = -sum_t om_t W r_t.
+ * No output may overlap x0, u, fext, dyn, x_obs or tick_w.  What is NOT differentiated: the parameters
+ * (cpmpc_sim_rollout_gn_batch), the external forces and dt; the wrap of the pole angles has unit derivative.  A problem with
+ * non-finite data has non-finite outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size, a negative or non-finite w_host entry and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before
+ * any device is needed. */
+typedef struct cpmpc_sim_rollout_gn_x0 {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_rollout_gn_x0) */
+  const void* x0;         /* [NX][B], read only: the point the fit is linearised at */
+  const void* u;          /* [T][B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* x_obs;      /* [T][NX][B] the recorded x_{t+1}; required where cost, g or H is asked for */
+  const double* w_host;   /* NX residual weights >= 0, or NULL: ones (zeros = that state was not measured) */
+  const void* tick_w;     /* [T][B] per-sample weights or NULL: ones (0 = that sample is missing) */
+  void* cost;             /* [B] or NULL */
+  void* g;                /* [NX][B] or NULL */
+  void* H;                /* [NX*NX][B] or NULL */
+  void* Phi_final;        /* [NX*NX][B] or NULL */
+  void* x_final;          /* [NX][B] or NULL */
+} cpmpc_sim_rollout_gn_x0;
+int cpmpc_sim_rollout_gn_x0_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                  const cpmpc_sim_rollout_gn_x0* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
