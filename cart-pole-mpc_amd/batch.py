@@ -1265,6 +1265,128 @@ def sim_estimate_state(params, dt, state, u, x_obs, iterations=8, damping=0.0, w
     return {"x0": x0, "x_final": cur["x_final"], "cost": cur["cost"], "H": cur["H"], "ok": live.to(torch.int32)}
 
 
+def sim_ekf(params, dt, state, cov, u, y, weights, process_noise=None, tick_weights=None, fext=None, f_base=(0.0, 0.0),
+            f_mass=(0.0, 0.0), model="single", want=("x_final", "P_final")):
+    """The extended Kalman filter of B plants over the T ticks of u [T, B], in ONE launch (include/cpmpc.h:
+    cpmpc_sim_ekf_batch): the recursive counterpart of sim_estimate_state.  From `state` [nx, B] with covariance `cov`
+    [nx, nx, B] (its lower triangle cov[j, k], k <= j, is what is read; neither is changed), per tick
+        predict   x- = the plant's tick from x under u[t],   P- = A P A^T + diag(process_noise),  A the tick's
+                  sim_step_jacobian A at the filtered x,
+        update    one measured state i at a time, where rho_i = tick_weights[t] weights[i] > 0:
+                  s = P_ii + 1 / rho_i,  nu = wrap(y[t][i] - x_i),  x += P[:, i] nu / s,  P -= P[:, i] P[i, :] / s.
+    weights: nx numbers >= 0 (None: ones), the INVERSE VARIANCES of the measurements y [T, nx, B] (y[t] is what was measured
+    after tick t) -- the convention of sim_rollout_gauss_newton_x0's weights; 0 says that state is not measured (encoders with
+    0.01 rms noise: (1e4, 1e4, 0, 0)).  process_noise: nx variances >= 0 added to P's diagonal once a tick (None: zeros).
+    tick_weights: [T, B] or None (ones); 0 says that sample is missing: x and P stay bitwise what the prediction left.  y may
+    be None where every weight is 0.  The tick's A and the covariance stay on the device; no matrix is inverted.
+
+    Returns a dict with the entries named in `want`,
+        "x_final" [nx, B]      the filtered state after the last tick -- what ClosedLoop.set_state() takes,
+        "P_final" [nx, nx, B]  its covariance, exactly symmetric,
+        "xs"      [T, nx, B]   the filtered state after every tick,
+        "nis"     [B]          the normalised squared innovations nu^2 / s added up: about one per scalar measurement where
+                               weights and process_noise fit the data, far more where a sensor has failed.
+    T = 1 is the per-tick filter (StateFilter) and the arrival-cost update of a moving horizon (WindowEstimator's prior_cov).
+    params (np numbers or an [np, B] tensor), dt and the forces as sim_rollout_states'."""
+    want = _want_tuple(want, ("x_final", "P_final", "xs", "nis"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimEkf(struct_size=C.sizeof(capi.SimEkf))
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    _require_cuda_tensor(cov, "cov", dtp, (nx, nx, B))
+    a.P0 = cov.data_ptr()
+    if y is not None:
+        _require_cuda_tensor(y, "y", dtp, (T, nx, B))
+        a.y = y.data_ptr()
+    w_host = q_host = None   # read by the call itself, before it returns
+    if weights is not None:
+        w_host = capi.dbl_array(weights, nx)
+        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
+    if y is None and (w_host is None or any(v > 0 for v in w_host)):
+        raise ValueError("y (the measurements) is required where a weight is > 0")
+    if process_noise is not None:
+        q_host = capi.dbl_array(process_noise, nx)
+        a.q_host = C.cast(q_host, C.POINTER(C.c_double))
+    if tick_weights is not None:
+        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
+        a.tick_w = tick_weights.data_ptr()
+    res = _alloc_outputs(a, want, {"x_final": ("x_final", (nx, B)), "P_final": ("P_final", (nx, nx, B)),
+                                   "xs": ("xs", (T, nx, B)), "nis": ("nis", (B,))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_ekf_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a), _stream_ptr()))
+    return res
+
+
+def _full_covariance(cov, nx, batch, dtype, name):
+    """cov [nx, B] (a diagonal) or [nx, nx, B] -> a fresh [nx, nx, B] tensor"""
+    _require_cuda_tensor(cov, name, dtype)
+    if tuple(cov.shape) == (nx, batch):
+        return torch.diag_embed(cov.t()).permute(1, 2, 0).contiguous()
+    if tuple(cov.shape) == (nx, nx, batch):
+        return cov.detach().clone()
+    raise ValueError("%s must be [%d, B] or [%d, %d, B]" % (name, nx, nx, nx))
+
+
+class StateFilter:
+    """A recursive state estimator for B plants: the extended Kalman filter, one sim_ekf launch of one tick per push() -- the
+    recursive counterpart of WindowEstimator, at the cost of about one plant tick with its Jacobian.  Per tick the caller
+    push()es the control it applied and what it then measured and gets the current state [nx, B] -- what
+    ClosedLoop.set_state() takes; .state and .cov hold the current state and its covariance [nx, nx, B], .nis [B] the last
+    tick's normalised squared innovations.  Nothing here waits for the device."""
+
+    def __init__(self, params, dt, batch, cov0, weights, process_noise, state=None, dtype=torch.float64, device=None,
+                 model="single", fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0)):
+        """cov0: the covariance of the first state, [nx, B] (a diagonal) or [nx, nx, B].  weights: the measurements' inverse
+        variances, process_noise: the variances added per tick (sim_ekf).  state [nx, B]: the first state (default: the
+        plants hanging at rest, BatchSimulator's initial state).  params, dt and the forces are those of every tick."""
+        self.model = model
+        _, self.nx, self.np = _model_dims(model)
+        if device is None:
+            device = torch.cuda.current_device()
+        self.device = torch.device("cuda", int(device)) if not isinstance(device, torch.device) else device
+        self.dtype, self.batch = dtype, int(batch)
+        self.params, self.dt, self.weights, self.process_noise = params, float(dt), weights, process_noise
+        self.forces = dict(fext=fext, f_base=f_base, f_mass=f_mass)
+        if state is None:
+            state = BatchSimulator(self.batch, dtype=dtype, device=self.device.index, model=model).get_state()
+        _require_cuda_tensor(state, "state", dtype, (self.nx, self.batch))
+        self.state = state.detach().clone()
+        self.cov = _full_covariance(cov0, self.nx, self.batch, dtype, "cov0")
+        self.nis = None
+
+    def push(self, u, y, tick_weight=None):
+        """One more tick: u [B] the control held over it, y [nx, B] the measurement after it (the rows of states whose
+        weight is 0 are not read), tick_weight [B] or None (ones; 0: the sample is missing, the tick is a prediction).
+        Returns the current state [nx, B], which .state holds too."""
+        _require_cuda_tensor(u, "u", self.dtype, (self.batch,))
+        _require_cuda_tensor(y, "y", self.dtype, (self.nx, self.batch))
+        if tick_weight is not None:
+            _require_cuda_tensor(tick_weight, "tick_weight", self.dtype, (self.batch,))
+            tick_weight = tick_weight.reshape(1, self.batch)
+        res = sim_ekf(self.params, self.dt, self.state, self.cov, u.reshape(1, self.batch), y.reshape(1, self.nx, self.batch),
+                      self.weights, process_noise=self.process_noise, tick_weights=tick_weight, model=self.model,
+                      want=("x_final", "P_final", "nis"), **self.forces)
+        self.state, self.cov, self.nis = res["x_final"], res["P_final"], res["nis"]
+        return self.state
+
+
+def _invert_spd_lanes(P):
+    """P [n, n, B], symmetric positive definite per lane (its lower triangle is read) -> P^-1 [n, n, B], symmetric: n unit
+    right-hand sides through _cholesky_solve_lanes.  A lane whose P is not positive definite gets NaNs."""
+    n = P.shape[0]
+    Hs = [[P[j, i] for i in range(n)] for j in range(n)]
+    zero, one = torch.zeros_like(P[0, 0]), torch.ones_like(P[0, 0])
+    cols = []
+    ok = None
+    for c in range(n):
+        x, pd = _cholesky_solve_lanes(Hs, [one if j == c else zero for j in range(n)])
+        cols.append(torch.stack(x))
+        ok = pd if ok is None else ok & pd
+    inv = torch.stack(cols, dim=1)
+    inv = 0.5 * (inv + inv.transpose(0, 1))
+    return torch.where(ok, inv, torch.full_like(inv, float("nan"))).contiguous()
+
+
 class WindowEstimator:
     """A moving-horizon state estimator for B plants: the last T controls and measurements on the device, and
     sim_estimate_state over them.  Per tick the caller push()es the control it applied and what it then measured, and
@@ -1272,14 +1394,22 @@ class WindowEstimator:
 
     The fit's unknown is the state at the START of the window.  It is warm-started from the previous estimate, advanced by
     one plant tick (one sim_rollout_states launch) whenever a full window drops its oldest sample; before the window is
-    full the estimator fits the ticks it has.  No arrival cost is carried from window to window (a rolling prior is not
-    built); estimate() passes a caller's prior / prior_info through.  Nothing here waits for the device."""
+    full the estimator fits the ticks it has.
+
+    The rolling prior (prior_cov given): the estimator keeps a prior mean and covariance of the window's first state -- at
+    first the constructor's `state` and prior_cov -- and, whenever a full window drops its oldest tick, advances them over
+    the dropped control, measurement and tick weight by one extended-Kalman-filter step (one sim_ekf launch of one tick):
+    what the dropped samples said is kept as the arrival cost, which estimate() hands to sim_estimate_state as `prior` and
+    prior_info = the covariance's inverse.  `weights` are then the measurements' inverse variances (sim_ekf).  Without
+    prior_cov no arrival cost is carried from window to window and everything is as it was.  Either way estimate() passes
+    a caller's own prior / prior_info through, and they take precedence.  Nothing here waits for the device."""
 
     def __init__(self, params, dt, batch, window, state=None, dtype=torch.float64, device=None, model="single", weights=None,
-                 fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0)):
+                 fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), prior_cov=None, process_noise=None):
         """window: T >= 1 ticks.  state [nx, B]: the first guess of the state before the first pushed tick (default: the
         plants hanging at rest, BatchSimulator's initial state).  params, dt, the forces and weights are those of every
-        sim_estimate_state call."""
+        sim_estimate_state call.  prior_cov: None, or the covariance of `state`, [nx, B] (a diagonal) or [nx, nx, B]: the
+        rolling prior; process_noise: the nx variances its step adds per tick (None: zeros)."""
         self.model = model
         _, self.nx, self.np = _model_dims(model)
         if device is None:
@@ -1298,6 +1428,11 @@ class WindowEstimator:
         self.y = torch.zeros((self.window, self.nx, self.batch), dtype=dtype, device=self.device)
         self.w = torch.zeros((self.window, self.batch), dtype=dtype, device=self.device)
         self.count = 0                            # ticks held, at most `window` (a host counter: nothing is read back)
+        self.process_noise = process_noise
+        self.prior_mean = self.prior_cov = None   # the rolling prior of the window's first state
+        if prior_cov is not None:
+            self.prior_cov = _full_covariance(prior_cov, self.nx, self.batch, dtype, "prior_cov")
+            self.prior_mean = state.detach().clone()
 
     def push(self, u, y, tick_weight=None):
         """One more tick: u [B] the control held over it, y [nx, B] the measurement after it (the rows of states that the
@@ -1308,6 +1443,10 @@ class WindowEstimator:
         if tick_weight is not None:
             _require_cuda_tensor(tick_weight, "tick_weight", self.dtype, (self.batch,))
         if self.count == self.window:
+            if self.prior_cov is not None:   # the dropped tick goes into the arrival cost
+                res = sim_ekf(self.params, self.dt, self.prior_mean, self.prior_cov, self.u[:1], self.y[:1], self.weights,
+                              process_noise=self.process_noise, tick_weights=self.w[:1], model=self.model, **self.forces)
+                self.prior_mean, self.prior_cov = res["x_final"], res["P_final"]
             self.x0 = sim_rollout_states(self.params, self.dt, self.x0, self.u[:1], model=self.model, want="x_final",
                                          **self.forces)["x_final"]
             self.u, self.y, self.w = torch.roll(self.u, -1, 0), torch.roll(self.y, -1, 0), torch.roll(self.w, -1, 0)
@@ -1331,9 +1470,11 @@ class WindowEstimator:
         return self.x0, self.u[:n], self.y[:n], self.w[:n]
 
     def estimate(self, iterations=2, damping=0.0, prior=None, prior_info=None, want_result=False):
-        """sim_estimate_state over the ticks held, from the warm start; the estimate of the window's first state is the next
-        call's guess.  Returns the current state [nx, B]; with want_result, (that, sim_estimate_state's dict)."""
+        """sim_estimate_state over the ticks held, from the warm start, with the rolling prior as the arrival cost where
+        the estimator keeps one; the estimate of the window's first state is the next call's guess.  Returns the current state [nx, B]; with want_result, (that, sim_estimate_state's dict)."""
         x0, u, y, w = self.held()
+        if prior is None and prior_info is None and self.prior_cov is not None:
+            prior, prior_info = self.prior_mean, _invert_spd_lanes(self.prior_cov)
         res = sim_estimate_state(self.params, self.dt, x0, u, y, iterations=iterations, damping=damping, weights=self.weights,
                                  tick_weights=w, prior=prior, prior_info=prior_info, model=self.model, **self.forces)
         self.x0 = res["x0"]

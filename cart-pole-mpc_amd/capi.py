@@ -51,7 +51,7 @@ SYMBOLS = [
     "cpmpc_sim_step_jac_batch", "cpmpc_sim_step_jac_batch_host",
     "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
     "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch", "cpmpc_sim_rollout_gn_batch",
-    "cpmpc_sim_rollout_gn_x0_batch",
+    "cpmpc_sim_rollout_gn_x0_batch", "cpmpc_sim_ekf_batch",
 ]
 
 
@@ -331,6 +331,29 @@ class SimRolloutGnX0(C.Structure):
     ]
 
 
+class SimEkf(C.Structure):
+    """cpmpc_sim_ekf: device pointers of cpmpc_sim_ekf_batch; x0, P0 (its lower triangle), u, dyn, the measurements y and the
+    per-sample weights tick_w are read, w_host (inverse variances of the measurement) and q_host (process-noise variances) are
+    NX host doubles each, x_final, P_final, xs and nis are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("P0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("y", C.c_void_p),
+        ("tick_w", C.c_void_p),
+        ("w_host", C.POINTER(C.c_double)),
+        ("q_host", C.POINTER(C.c_double)),
+        ("x_final", C.c_void_p),
+        ("P_final", C.c_void_p),
+        ("xs", C.c_void_p),
+        ("nis", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -465,6 +488,7 @@ def load():
     L.cpmpc_sim_rollout_vjp_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutVjp), vp]
     L.cpmpc_sim_rollout_gn_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutGn), vp]
     L.cpmpc_sim_rollout_gn_x0_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutGnX0), vp]
+    L.cpmpc_sim_ekf_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimEkf), vp]
     _lib = L
     return L
 

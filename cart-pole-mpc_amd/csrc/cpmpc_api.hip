@@ -1082,6 +1082,41 @@ extern "C" int cpmpc_sim_rollout_gn_x0_batch(int model, int dtype, int64_t B, co
   });
 }
 
+// ---- the extended Kalman filter over T ticks (sim_ekf_kernels.hpp) ------------------------------------------------------
+static int check_sim_ekf_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                              const cpmpc_sim_ekf* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_ekf)");
+  int rc = check_rollout_common("cpmpc_sim_ekf", a->struct_size, sizeof(cpmpc_sim_ekf), a->x0, a->u, dyn_shared_host, a->dyn,
+                                dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->P0) return fail(CPMPC_ERR_INVALID_ARG, "null argument (P0)");
+  if (!a->x_final && !a->P_final && !a->xs && !a->nis) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  bool measured = !a->w_host;  // NULL: ones
+  for (size_t i = 0; i < nx; ++i) {
+    if (a->w_host && (!(a->w_host[i] >= 0.0) || !std::isfinite(a->w_host[i])))
+      return fail(CPMPC_ERR_INVALID_ARG, "w_host[%zu] must be finite and >= 0", i);
+    if (a->q_host && (!(a->q_host[i] >= 0.0) || !std::isfinite(a->q_host[i])))
+      return fail(CPMPC_ERR_INVALID_ARG, "q_host[%zu] must be finite and >= 0", i);
+    if (a->w_host && a->w_host[i] > 0.0) measured = true;
+  }
+  if (measured && !a->y) return fail(CPMPC_ERR_INVALID_ARG, "a state is measured (w_host > 0) without y");
+  const ArraySpan outs[4] = {{a->x_final, nx, "x_final"}, {a->P_final, nx * nx, "P_final"}, {a->xs, nt * nx, "xs"},
+                             {a->nis, 1, "nis"}};
+  const ArraySpan ins[7] = {{a->x0, nx, "x0"},      {a->P0, nx * nx, "P0"}, {a->u, nt, "u"},          {a->fext, 4, "fext"},
+                            {a->dyn, np, "dyn"},    {a->y, nt * nx, "y"},   {a->tick_w, nt, "tick_w"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_ekf_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                   const cpmpc_sim_ekf* a, void* stream) {
+  int rc = check_sim_ekf_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_ekf(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

@@ -251,6 +251,10 @@ struct Engine {
   // H, Phi_final, x_final of `a` that are not null (sim_rollout_gn_x0_kernels.hpp)
   void (*sim_rollout_gn_x0)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                             const cpmpc_sim_rollout_gn_x0* a, hipStream_t stream);
+  // the extended Kalman filter over T ticks in one launch: x_final, P_final, xs, nis of `a` that are not null
+  // (sim_ekf_kernels.hpp)
+  void (*sim_ekf)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_ekf* a,
+                  hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

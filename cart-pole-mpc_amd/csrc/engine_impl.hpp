@@ -19,6 +19,7 @@
 #include "sim_rollout_kernels.hpp"
 #include "sim_rollout_gn_kernels.hpp"
 #include "sim_rollout_gn_x0_kernels.hpp"
+#include "sim_ekf_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -654,6 +655,24 @@ static void sim_rollout_gn_x0_impl(int64_t B, const double* dyn_shared_host, int
   });
 }
 
+// ---- the extended Kalman filter over T ticks, one launch (sim_ekf_kernels.hpp) ----------------------------------------
+template <typename R, typename M>
+static void sim_ekf_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_ekf* a,
+                         hipStream_t stream) {
+  StateWeights<R, M::NX> sw, q;
+  for (int i = 0; i < M::NX; ++i) {
+    sw.w[i] = a->w_host ? (R)a->w_host[i] : R(1);
+    q.w[i] = a->q_host ? (R)a->q_host[i] : R(0);
+  }
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    hipLaunchKernelGGL((sim_ekf_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                       plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->P0, (const R*)a->u, (const R*)a->y, sw, q,
+                       (const R*)a->tick_w, (R*)a->x_final, (R*)a->P_final, (R*)a->xs, (R*)a->nis);
+  });
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
 // linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
@@ -791,6 +810,6 @@ static int debug_read_impl(int which, unsigned long long* out) {
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
                              &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>, &sim_dyn_impl<R, M>,           \
                              &sim_param_jac_impl<R, M>,   &sim_rollout_impl<R, M>,     &sim_rollout_vjp_impl<R, M>,   \
-                             &sim_rollout_gn_impl<R, M>,  &sim_rollout_gn_x0_impl<R, M>};                            \
+                             &sim_rollout_gn_impl<R, M>,  &sim_rollout_gn_x0_impl<R, M>, &sim_ekf_impl<R, M>};        \
     return &e;                                                                                                       \
   }

@@ -625,6 +625,52 @@ typedef struct cpmpc_sim_rollout_gn_x0 {
 int cpmpc_sim_rollout_gn_x0_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                   const cpmpc_sim_rollout_gn_x0* a, void* stream);
 
+/* The EXTENDED KALMAN FILTER of B plants over T ticks in one launch: the recursive counterpart of the call above.  From the
+ * state x0 [NX][B] and its covariance P0 [NX*NX][B] (element (j, k) at field j*NX + k; ONLY THE LOWER TRIANGLE, k <= j, IS
+ * READ), per tick t = 0 .. T-1
+ *     predict   x- = Step(x, u[t], dt),   P- = A_t P A_t^T + diag(q_host)      (A_t the tick's dx+/dx at the filtered x,
+ *                                                                               as cpmpc_sim_step_jac_batch's A)
+ *     update    for every state i in index order with rho_i = om_t w_host[i] > 0,  om_t = tick_w ? tick_w[t] : 1:
+ *                   s = P_ii + 1/rho_i,   nu = wrap_i(y[t][i] - x_i),   K = P[:, i] / s
+ *                   x += K nu,   P -= K P[i, :],   nis += nu^2 / s
+ *               then the pole angles of x are wrapped (where an update acted).
+ * w_host are the INVERSE VARIANCES of the measurement y [T][NX][B] (y[t] is the measured x_{t+1}), the convention of the
+ * weights of cpmpc_sim_rollout_gn_x0_batch; NULL: ones.  A weight of 0 says that state is not measured (positions only with
+ * 0.01 rms noise: 1e4, 1e4, 0, 0), a tick weight of 0 that the sample is missing: there x and P stay bitwise what the
+ * prediction left and y is not read.  q_host are NX process-noise VARIANCES >= 0, added to P's diagonal once a tick; NULL:
+ * zeros.  The measurement covariance is diagonal, so the scalar updates in sequence ARE the joint update; no matrix is
+ * inverted.  The tick's A stays in registers and the covariance on the device: nothing per tick goes to memory but xs.
+ *     x_final [NX][B], P_final [NX*NX][B] (full and exactly symmetric), xs [T][NX][B] the filtered state after every
+ *     tick, nis [B] the normalised squared innovations added up (about one per scalar measurement where q and w are
+ *     consistent with the data; far more where a sensor has failed).
+ * Every output is nullable, only those given are stored, at least one must be given, and each is bitwise the same
+ * whichever others are asked for.  T = 1 is the per-tick filter (x_final and P_final may be handed back as the next call's
+ * x0 and P0) and the arrival-cost update of a moving horizon.  y is required where some w_host[i] > 0.  dt = 0: A = I, the
+ * linear Kalman filter of a constant state.  No output may overlap x0, P0, u, fext, dyn, y or tick_w.  A problem with
+ * non-finite data has non-finite outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size, a negative or non-finite w_host or q_host entry and the pointer rules above -> CPMPC_ERR_INVALID_ARG,
+ * before any device is needed. */
+typedef struct cpmpc_sim_ekf {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_ekf) */
+  const void* x0;         /* [NX][B], read only: the filtered state before the first tick */
+  const void* P0;         /* [NX*NX][B], read only: its covariance; the lower triangle is read */
+  const void* u;          /* [T][B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* y;          /* [T][NX][B] the measured x_{t+1}; required where some w_host[i] > 0 */
+  const void* tick_w;     /* [T][B] per-sample weights or NULL: ones (0 = that sample is missing) */
+  const double* w_host;   /* NX inverse variances of the measurement >= 0, or NULL: ones (0 = not measured) */
+  const double* q_host;   /* NX process-noise variances >= 0 added once a tick, or NULL: zeros */
+  void* x_final;          /* [NX][B] or NULL */
+  void* P_final;          /* [NX*NX][B] or NULL */
+  void* xs;               /* [T][NX][B] or NULL */
+  void* nis;              /* [B] or NULL */
+} cpmpc_sim_ekf;
+int cpmpc_sim_ekf_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                        const cpmpc_sim_ekf* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
