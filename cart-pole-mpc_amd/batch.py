@@ -123,7 +123,8 @@ class BatchOptimization:
         every problem (include/cpmpc.h, CPMPC_CREATE_STRICT_HORIZON).  By default every horizon the reference accepts is
         accepted, with one warning per process; allow_long_horizon=True silences the warning.
         refine_qp: True / False force on / off the refinement of the whole QP solution in the fp64 fused kernels
-        (CPMPC_CREATE_[NO_]REFINE_QP: 7 % slower); None = the library's default: on when u_cost_weight < 0.05.
+        (CPMPC_CREATE_[NO_]REFINE_QP: 7 % slower); None = the library's default: on when u_cost_weight < 0.05 and, for
+        the 6-state model, when th_final_cost_weight >= 0 with th_dot_final_cost_weight < 0 (include/cpmpc.h).
         wide_qp: True / False force on / off that float32 handles carry the QP's whole terminal part in double
         (CPMPC_CREATE_[NO_]WIDE_QP: cold starts end where a float solve can -- 3x to 20x closer to the double check for the
         4-state model at 3.8 % of the throughput, 70x to 900x for the 6-state one at 0 - 5 %); None = the library's

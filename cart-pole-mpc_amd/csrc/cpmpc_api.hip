@@ -216,8 +216,15 @@ static int create_impl(const cpmpc_params* params, const cpmpc_solver_opts* opts
   // beyond the parity horizon: there AUTO takes the split pipeline with two passes of refinement with residuals from the
   // original data (refine_passes below), and the lanes on which the kernels (not the CPU check) are at fault go from 34 of
   // 8 192 to 1 at N = 160, as many as the CPU check (profiles/r06_long_horizon_probe_{8192,16384}.json)
+  // and for the 6-state model where the pole angles are cost rows while their rates are equalities: there the condensed solve
+  // of the first QP of a cold start is 7e-9 from an extended-precision solve where the CPU check's dense one is 2e-10 and the
+  // refined one 7e-12, and four iterations carry that to 5e-5 on a lane on which the CPU check stays within 2e-8
+  // (tests/test_gpu_double_parity.py, 40/8; include/cpmpc.h, CPMPC_CREATE_REFINE_QP)
+  const bool angle_cost_rate_equality =
+      model == CPMPC_MODEL_DOUBLE && params->th_final_cost_weight >= 0.0 && params->th_dot_final_cost_weight < 0.0;
   s->refine_qp = (flags & CPMPC_CREATE_REFINE_QP) != 0 ||
-                 (!(flags & CPMPC_CREATE_NO_REFINE_QP) && (params->u_cost_weight < kRefineBelowUCostWeight || s->beyond_parity));
+                 (!(flags & CPMPC_CREATE_NO_REFINE_QP) &&
+                  (params->u_cost_weight < kRefineBelowUCostWeight || s->beyond_parity || angle_cost_rate_equality));
   // split pipeline: one pass; two beyond the parity horizon (tools/long_horizon_refine_study.py, first QP of 300 cold starts at
   // 1.6 s against a long-double solve: worst lane 3.5e-5 condensed, 1.6e-11 after one pass, 1.2e-13 after two -- the dense
   // pivoted LU of the CPU check: 1.1e-12; further passes change nothing)

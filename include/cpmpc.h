@@ -169,6 +169,13 @@ void cpmpc_destroy(cpmpc_solver* s);
  *                 and, whatever the weights, definitions whose friction the explicit RK4 cannot follow (v_mu_b = 1e-7
  *                 with mu_b > 0: a slope of 1e5..1e6 1/s against a stability limit of 280 1/s at 10 ms; |Phi| reaches
  *                 1e4 per interval, the terminal system's condition 1e18): 281 of 923 648 lanes, 72 with it.
+ *              And for CPMPC_MODEL_DOUBLE when th_final_cost_weight >= 0 with th_dot_final_cost_weight < 0 (the pole angles
+ *              cost rows, their rates equalities): the first QP of a cold start is 7e-9 from an extended-precision solve
+ *              without the refinement (the CPU check: 2e-10) and 7e-12 with it, and on a lane on which the CPU check ends
+ *              within 2e-8 of that solve after four iterations the kernels end 5e-5 from it without and 1e-7 with it
+ *              (40 steps, spacing 8; tests/test_gpu_double_parity.py).  The rule reads the handle's parameters: a caller
+ *              who sets such rows per problem (terminal_weights) on a handle whose own rows are not of that kind passes
+ *              CPMPC_CREATE_REFINE_QP.
  *              Both pipelines; ignored by CPMPC_F32 handles.  cpmpc_refines_qp() tells what a handle does. */
 #define CPMPC_CREATE_ALLOW_LONG_HORIZON 1u /* accepted; silences the long-horizon warning */
 #define CPMPC_CREATE_REFINE_QP 2u

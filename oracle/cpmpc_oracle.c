@@ -524,6 +524,11 @@ static int num_states(const orc_opt_params* p) { /* optimization.hpp:52 */
   return (int)(p->window_length / p->state_spacing) + 1;
 }
 
+/* Optional override of the weights, row by row in state order (tests only): what orc_opt_params cannot say, the two poles of
+ * the double pendulum with different rows.  Per thread; set by step_batch_cold_rows around one problem and null otherwise, so
+ * every other entry point computes exactly what it did without it. */
+static __thread const double* g_terminal_rows = NULL;
+
 /* Terminal weights and targets in BuildProblem order (optimization.cc:236-267).  For the double pendulum
  * (no optimizer in the reference) th_final / th_dot_final apply to both poles and both are to be upright. */
 static void terminal_spec(const orc_model* m, const orc_opt_params* p, double set_point, double* w, double* tgt) {
@@ -542,6 +547,8 @@ static void terminal_spec(const orc_model* m, const orc_opt_params* p, double se
       tgt[t] = 0.0;
     }
   }
+  if (g_terminal_rows)
+    for (int t = 0; t < m->nx; ++t) w[t] = g_terminal_rows[t];
 }
 
 static void problem_shape(const orc_model* m, const orc_opt_params* p, int* dim, int* n_eq, int* n_cost) {
@@ -1206,9 +1213,12 @@ void orc_sim_step_model(int model, const double* params, double dt, double u, do
 /* batch driver                                                                                 */
 /* ------------------------------------------------------------------------------------------- */
 
-int orc_step_batch_cold_model(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
-                              double set_point, int64_t B, const double* x0_soa, double* u_out_soa,
-                              double* pred_out_soa, int32_t* status, int32_t* iters, int num_threads) {
+/* rows_soa: null, or terminal weights [nx][B] in state order that replace the four *_final_cost_weight of p for that problem
+ * (>= 0 a cost row, < 0 an equality row). */
+static int step_batch_cold_rows(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
+                                double set_point, int64_t B, const double* x0_soa, const double* rows_soa,
+                                double* u_out_soa, double* pred_out_soa, int32_t* status, int32_t* iters,
+                                int num_threads) {
   const int N = (int)p->window_length;
   const int n = model_of(model)->nx;
   int used = 1;
@@ -1229,8 +1239,14 @@ int orc_step_batch_cold_model(int model, const orc_opt_params* p, const orc_solv
       orc_opt_reset(opt);
       double x0[ORC_MAXNX];
       for (int t = 0; t < n; ++t) x0[t] = x0_soa[(int64_t)t * B + b];
+      double rows[ORC_MAXNX];
+      if (rows_soa) {
+        for (int t = 0; t < n; ++t) rows[t] = rows_soa[(int64_t)t * B + b];
+        g_terminal_rows = rows;
+      }
       orc_solver_summary sum;
       orc_opt_step(opt, x0, dyn, set_point, u, pred_out_soa ? pred : NULL, NULL, NULL, &sum);
+      g_terminal_rows = NULL;
       for (int k = 0; k < N; ++k) u_out_soa[(int64_t)k * B + b] = u[k];
       if (pred_out_soa)
         for (int k = 0; k < N; ++k)
@@ -1243,6 +1259,21 @@ int orc_step_batch_cold_model(int model, const orc_opt_params* p, const orc_solv
     orc_opt_destroy(opt);
   }
   return used;
+}
+
+int orc_step_batch_cold_model(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
+                              double set_point, int64_t B, const double* x0_soa, double* u_out_soa,
+                              double* pred_out_soa, int32_t* status, int32_t* iters, int num_threads) {
+  return step_batch_cold_rows(model, p, o, dyn, set_point, B, x0_soa, NULL, u_out_soa, pred_out_soa, status, iters,
+                              num_threads);
+}
+
+int orc_step_batch_cold_rows_model(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
+                                   double set_point, int64_t B, const double* x0_soa, const double* rows_soa,
+                                   double* u_out_soa, double* pred_out_soa, int32_t* status, int32_t* iters,
+                                   int num_threads) {
+  return step_batch_cold_rows(model, p, o, dyn, set_point, B, x0_soa, rows_soa, u_out_soa, pred_out_soa, status, iters,
+                              num_threads);
 }
 
 int orc_step_batch_cold(const orc_opt_params* p, const orc_solver_opts* o, const double dyn[9],

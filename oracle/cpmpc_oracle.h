@@ -210,6 +210,13 @@ int orc_step_batch_cold_model(int model, const orc_opt_params* p, const orc_solv
                               const double* dyn, double set_point, int64_t B, const double* x0_soa,
                               double* u_out_soa, double* pred_out_soa, int32_t* status, int32_t* iters,
                               int num_threads);
+/* The same with terminal weights per problem and per ROW: rows_soa[nx][B] in state order (nullable: then exactly the call
+ * above) replaces the four *_final_cost_weight of p -- >= 0 a cost row, < 0 an equality row -- so that the two poles of the
+ * double pendulum can have different rows, which orc_opt_params cannot express (tests of the kernels' per-problem weights). */
+int orc_step_batch_cold_rows_model(int model, const orc_opt_params* p, const orc_solver_opts* o,
+                                   const double* dyn, double set_point, int64_t B, const double* x0_soa,
+                                   const double* rows_soa, double* u_out_soa, double* pred_out_soa, int32_t* status,
+                                   int32_t* iters, int num_threads);
 
 /* ---- batch driver (cpu_baseline leg of bench.py; OpenMP over problems) --------------------- */
 /* SoA inputs like the product C-ABI: x0[4][B]; cold start for every problem.

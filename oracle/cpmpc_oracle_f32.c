@@ -60,6 +60,7 @@
 #define orc_solve orcf_solve
 #define orc_step_batch_cold orcf_step_batch_cold
 #define orc_step_batch_cold_model orcf_step_batch_cold_model
+#define orc_step_batch_cold_rows_model orcf_step_batch_cold_rows_model
 #define orc_optimization orcf_optimization
 typedef struct orcf_optimization orcf_optimization;
 

@@ -56,6 +56,7 @@
 #define orc_solve orcld_solve
 #define orc_step_batch_cold orcld_step_batch_cold
 #define orc_step_batch_cold_model orcld_step_batch_cold_model
+#define orc_step_batch_cold_rows_model orcld_step_batch_cold_rows_model
 #define orc_optimization orcld_optimization
 typedef struct orcld_optimization orcld_optimization;
 
@@ -78,9 +79,10 @@ typedef struct orcld_optimization orcld_optimization;
 
 /* double in, double out; everything in between in long double.  Same argument meaning as orc_step_batch_cold_model;
  * eq_l1_out (nullable) receives the final |c|_1 of each problem. */
-int orcld_step_batch_cold_d(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
-                            double set_point, int64_t B, const double* x0_soa, double* u_out_soa, int32_t* status,
-                            int32_t* iters, int32_t* ls_evals, double* eq_l1_out, int num_threads) {
+static int step_batch_cold_rows_d(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
+                                  double set_point, int64_t B, const double* x0_soa, const double* rows_soa,
+                                  double* u_out_soa, int32_t* status, int32_t* iters, int32_t* ls_evals,
+                                  double* eq_l1_out, int num_threads) {
   const int N = (int)p->window_length;
   const int n = orcld_model_nx(model), np = orcld_model_np(model);
   long double dyn_ld[16];
@@ -102,8 +104,14 @@ int orcld_step_batch_cold_d(int model, const orc_opt_params* p, const orc_solver
       orcld_opt_reset(opt);
       long double x0[ORC_MAXNX];
       for (int t = 0; t < n; ++t) x0[t] = x0_soa[(int64_t)t * B + b];
+      long double rows[ORC_MAXNX];
+      if (rows_soa) {
+        for (int t = 0; t < n; ++t) rows[t] = rows_soa[(int64_t)t * B + b];
+        g_terminal_rows = rows;
+      }
       orc_solver_summary sum;
       orcld_opt_step(opt, x0, dyn_ld, (long double)set_point, u, NULL, NULL, NULL, &sum);
+      g_terminal_rows = NULL;
       for (int k = 0; k < N; ++k) u_out_soa[(int64_t)k * B + b] = (double)u[k];
       if (status) status[b] = sum.termination_state;
       if (iters) iters[b] = sum.iterations;
@@ -114,4 +122,20 @@ int orcld_step_batch_cold_d(int model, const orc_opt_params* p, const orc_solver
     orcld_opt_destroy(opt);
   }
   return used;
+}
+
+int orcld_step_batch_cold_d(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
+                            double set_point, int64_t B, const double* x0_soa, double* u_out_soa, int32_t* status,
+                            int32_t* iters, int32_t* ls_evals, double* eq_l1_out, int num_threads) {
+  return step_batch_cold_rows_d(model, p, o, dyn, set_point, B, x0_soa, NULL, u_out_soa, status, iters, ls_evals, eq_l1_out,
+                                num_threads);
+}
+
+/* The same with terminal weights per problem and per row (orc_step_batch_cold_rows_model): rows_soa[nx][B], nullable. */
+int orcld_step_batch_cold_rows_d(int model, const orc_opt_params* p, const orc_solver_opts* o, const double* dyn,
+                                 double set_point, int64_t B, const double* x0_soa, const double* rows_soa,
+                                 double* u_out_soa, int32_t* status, int32_t* iters, int32_t* ls_evals, double* eq_l1_out,
+                                 int num_threads) {
+  return step_batch_cold_rows_d(model, p, o, dyn, set_point, B, x0_soa, rows_soa, u_out_soa, status, iters, ls_evals,
+                                eq_l1_out, num_threads);
 }

@@ -194,6 +194,10 @@ def lib():
                                             C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32), C.c_int]
     L.orc_step_batch_cold_model.restype = C.c_int
+    L.orc_step_batch_cold_rows_model.argtypes = [C.c_int, C.POINTER(OptParams), C.POINTER(SolverOpts), _dp, C.c_double,
+                                                 C.c_int64, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32),
+                                                 C.POINTER(C.c_int32), C.c_int]
+    L.orc_step_batch_cold_rows_model.restype = C.c_int
     _lib = L
     return L
 
@@ -210,6 +214,15 @@ def lib_ld():
         L.orcld_step_batch_cold_d.argtypes = [C.c_int, C.POINTER(OptParams), C.POINTER(SolverOpts), _dp, C.c_double,
                                               C.c_int64, _dp, _dp, ip, ip, ip, _dp, C.c_int]
         L.orcld_step_batch_cold_d.restype = C.c_int
+        L.orcld_step_batch_cold_rows_d.argtypes = [C.c_int, C.POINTER(OptParams), C.POINTER(SolverOpts), _dp, C.c_double,
+                                                   C.c_int64, _dp, _dp, _dp, ip, ip, ip, _dp, C.c_int]
+        L.orcld_step_batch_cold_rows_d.restype = C.c_int
+        lp = C.POINTER(C.c_longdouble)
+        L.orcld_opt_create_model.argtypes = [C.POINTER(OptParams), C.POINTER(SolverOpts), C.c_int]
+        L.orcld_opt_create_model.restype = C.c_void_p
+        L.orcld_opt_destroy.argtypes = [C.c_void_p]
+        L.orcld_opt_step.argtypes = [C.c_void_p, lp, lp, C.c_longdouble, lp, lp, lp, lp, C.POINTER(SolverSummary)]
+        L.orcld_opt_step.restype = C.c_int
         _lib_ld = L
     return _lib_ld
 
@@ -485,6 +498,34 @@ class Optimization:
         return StepOutputs(state.copy(), prev, s, u, pred, guess, z)
 
 
+class OptimizationLd:
+    """Optimization in EXTENDED precision (oracle/cpmpc_oracle_ld.c), for warm-started steps: the arbiter that
+    step_batch_cold_ld is for cold ones.  step() -> (u [N] rounded to double, termination state, iterations)."""
+
+    def __init__(self, params, opts=None, model="single"):
+        self.params, self.model = params, MODELS[model]
+        self._L = lib_ld()
+        self._h = self._L.orcld_opt_create_model(C.byref(params), C.byref(opts) if opts is not None else None, self.model)
+        if not self._h:
+            raise ValueError("invalid OptimizationParams (optimization.cc:13-22 preconditions)")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.orcld_opt_destroy(self._h)
+            self._h = None
+
+    def step(self, state, dyn, set_point):
+        lp = C.POINTER(C.c_longdouble)
+        assert np.dtype(np.longdouble).itemsize == C.sizeof(C.c_longdouble)
+        state = np.ascontiguousarray(_vec(state, model_nx(self.model)), dtype=np.longdouble)
+        dyn = np.ascontiguousarray(_vec(dyn, model_np(self.model)), dtype=np.longdouble)
+        u = np.zeros(int(self.params.window_length), dtype=np.longdouble)
+        s = SolverSummary()
+        self._L.orcld_opt_step(self._h, state.ctypes.data_as(lp), dyn.ctypes.data_as(lp), C.c_longdouble(set_point),
+                               u.ctypes.data_as(lp), None, None, None, C.byref(s))
+        return u.astype(np.float64), s.termination_state, s.iterations
+
+
 class Simulator:
     """Oracle counterpart of pendulum::Simulator (simulator.hpp:10-29)."""
 
@@ -543,6 +584,49 @@ def step_batch_cold_ld(p, dyn, set_point, x0_soa, opts=None, num_threads=0, mode
     lib_ld().orcld_step_batch_cold_d(m, C.byref(p), C.byref(opts) if opts is not None else None, _ptr(dyn),
                                      float(set_point), B, _ptr(x0), _ptr(u), status.ctypes.data_as(ip),
                                      iters.ctypes.data_as(ip), evals.ctypes.data_as(ip), _ptr(eq), int(num_threads))
+    return u, status, iters, evals, eq
+
+
+def _terminal_rows(rows, nx, B):
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    assert rows.shape == (nx, B), (rows.shape, nx, B)
+    return rows
+
+
+def step_batch_cold_rows(p, dyn, set_point, x0_soa, rows, opts=None, want_pred=False, num_threads=0, model="single"):
+    """step_batch_cold with terminal weights per problem and per row: rows [nx, B] in state order (>= 0 a cost row, < 0 an
+    equality row) replaces the four *_final_cost_weight of p, so that the two poles of the 6-state model can differ."""
+    m = MODELS[model]
+    nx = model_nx(m)
+    x0 = np.ascontiguousarray(x0_soa, dtype=np.float64)
+    assert x0.ndim == 2 and x0.shape[0] == nx
+    B, N = x0.shape[1], int(p.window_length)
+    dyn, rows = _vec(dyn, model_np(m)), _terminal_rows(rows, nx, B)
+    u = np.zeros((N, B))
+    pred = np.zeros((N, nx, B)) if want_pred else None
+    status, iters = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    ip = C.POINTER(C.c_int32)
+    used = lib().orc_step_batch_cold_rows_model(
+        m, C.byref(p), C.byref(opts) if opts is not None else None, _ptr(dyn), float(set_point), B, _ptr(x0), _ptr(rows),
+        _ptr(u), _ptr(pred), status.ctypes.data_as(ip), iters.ctypes.data_as(ip), int(num_threads))
+    return u, pred, status, iters, used
+
+
+def step_batch_cold_rows_ld(p, dyn, set_point, x0_soa, rows, opts=None, num_threads=0, model="single"):
+    """step_batch_cold_ld with terminal weights per problem and per row (step_batch_cold_rows)."""
+    m = MODELS[model]
+    nx = model_nx(m)
+    x0 = np.ascontiguousarray(x0_soa, dtype=np.float64)
+    assert x0.ndim == 2 and x0.shape[0] == nx
+    B, N = x0.shape[1], int(p.window_length)
+    dyn, rows = _vec(dyn, model_np(m)), _terminal_rows(rows, nx, B)
+    u = np.zeros((N, B))
+    status, iters, evals = (np.zeros(B, dtype=np.int32) for _ in range(3))
+    eq = np.zeros(B)
+    ip = C.POINTER(C.c_int32)
+    lib_ld().orcld_step_batch_cold_rows_d(m, C.byref(p), C.byref(opts) if opts is not None else None, _ptr(dyn),
+                                          float(set_point), B, _ptr(x0), _ptr(rows), _ptr(u), status.ctypes.data_as(ip),
+                                          iters.ctypes.data_as(ip), evals.ctypes.data_as(ip), _ptr(eq), int(num_threads))
     return u, status, iters, evals, eq
 
 
