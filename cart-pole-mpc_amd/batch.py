@@ -1000,6 +1000,43 @@ def sim_rollout(params, dt, state, u, fext=None, f_base=(0.0, 0.0), f_mass=(0.0,
     return _SimRolloutFunction.apply(state, u, params, dt, fext, f_base, f_mass, model)
 
 
+def _window_inputs(a, field, rec, weights, tick_weights, dtp, T, nx, B):
+    """What the window calls read beside the plant's inputs, checked and set on the struct `a`: the recording `rec` [T, nx, B]
+    as `field` ("x_obs" / "y"), weights (nx numbers) as w_host, tick_weights [T, B] as tick_w, each or None -> the weights as the
+    host array that the call reads before it returns (the caller holds it until then), or None."""
+    if rec is not None:
+        _require_cuda_tensor(rec, field, dtp, (T, nx, B))
+        setattr(a, field, rec.data_ptr())
+    w_host = None
+    if weights is not None:
+        w_host = capi.dbl_array(weights, nx)
+        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
+    if tick_weights is not None:
+        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
+        a.tick_w = tick_weights.data_ptr()
+    return w_host
+
+
+def _gauss_newton_call(struct, symbol, final, in_params, params, dt, state, u, x_obs, weights, tick_weights, fext, f_base, f_mass,
+                       model, want):
+    """`symbol`, a Gauss-Newton window call, on the current stream with a `struct`: the unknowns are the np parameters
+    (in_params) or the initial state, `final` names d(last state)/d(unknowns)."""
+    want = _want_tuple(want, ("cost", "g", "H", final, "x_final"))
+    m, nx, npar = dims = _model_dims(model)
+    n = npar if in_params else nx
+    dtp = state.dtype
+    a = struct(struct_size=C.sizeof(struct))
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    if x_obs is None and any(w in ("cost", "g", "H") for w in want):
+        raise ValueError("x_obs (the recorded states) is required for cost, g and H")
+    _w_held = _window_inputs(a, "x_obs", x_obs, weights, tick_weights, dtp, T, nx, B)
+    res = _alloc_outputs(a, want, {"cost": ("cost", (B,)), "g": ("g", (n, B)), "H": ("H", (n, n, B)),
+                                   final: (final, (nx, n, B)), "x_final": ("x_final", (nx, B))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(getattr(capi.load(), symbol)(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a), _stream_ptr()))
+    return res
+
+
 def sim_rollout_gauss_newton(params, dt, state, u, x_obs, weights=None, tick_weights=None, fext=None, f_base=(0.0, 0.0),
                              f_mass=(0.0, 0.0), model="single", want=("cost", "g", "H")):
     """The forward mode of sim_rollout_states in the parameters and the Gauss-Newton normal equations of an output-error fit
@@ -1019,30 +1056,8 @@ def sim_rollout_gauss_newton(params, dt, state, u, x_obs, weights=None, tick_wei
 
     Several recorded windows of one plant: lay them side by side as columns (2 B columns for two windows, the parameters
     repeated) and add the windows' cost, g and H in torch before solving; the kernel knows nothing of it."""
-    want = _want_tuple(want, ("cost", "g", "H", "S_final", "x_final"))
-    m, nx, npar = dims = _model_dims(model)
-    dtp = state.dtype
-    a = capi.SimRolloutGn(struct_size=C.sizeof(capi.SimRolloutGn))
-    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
-    if x_obs is not None:
-        _require_cuda_tensor(x_obs, "x_obs", dtp, (T, nx, B))
-        a.x_obs = x_obs.data_ptr()
-    elif any(w in ("cost", "g", "H") for w in want):
-        raise ValueError("x_obs (the recorded states) is required for cost, g and H")
-    w_host = None
-    if weights is not None:
-        w_host = capi.dbl_array(weights, nx)   # read by the call itself, before it returns
-        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
-    if tick_weights is not None:
-        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
-        a.tick_w = tick_weights.data_ptr()
-    res = _alloc_outputs(a, want, {"cost": ("cost", (B,)), "g": ("g", (npar, B)), "H": ("H", (npar, npar, B)),
-                                   "S_final": ("S_final", (nx, npar, B)), "x_final": ("x_final", (nx, B))}, dtp, state.device)
-    with torch.cuda.device(state.device):
-        capi.check(capi.load().cpmpc_sim_rollout_gn_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
-                                                          _stream_ptr()))
-    return res
-
+    return _gauss_newton_call(capi.SimRolloutGn, "cpmpc_sim_rollout_gn_batch", "S_final", True, params, dt, state, u, x_obs,
+                              weights, tick_weights, fext, f_base, f_mass, model, want)
 
 def _cholesky_solve_lanes(Hs, gs, pivot_floor=0.0):
     """x = H^-1 g per lane for k x k systems given as lists of [B] tensors (Hs[j][i], i <= j, is read), solved on the
@@ -1173,30 +1188,8 @@ def sim_rollout_gauss_newton_x0(params, dt, state, u, x_obs, weights=None, tick_
     may be None where none of cost, g, H is asked for.  Phi never goes to memory and no per-tick Jacobian is formed.  params
     (np numbers or an [np, B] tensor), dt and the forces as sim_rollout_states'.  Not differentiated: the parameters
     (sim_rollout_gauss_newton), the external forces and dt."""
-    want = _want_tuple(want, ("cost", "g", "H", "Phi_final", "x_final"))
-    m, nx, npar = dims = _model_dims(model)
-    dtp = state.dtype
-    a = capi.SimRolloutGnX0(struct_size=C.sizeof(capi.SimRolloutGnX0))
-    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
-    if x_obs is not None:
-        _require_cuda_tensor(x_obs, "x_obs", dtp, (T, nx, B))
-        a.x_obs = x_obs.data_ptr()
-    elif any(w in ("cost", "g", "H") for w in want):
-        raise ValueError("x_obs (the recorded states) is required for cost, g and H")
-    w_host = None
-    if weights is not None:
-        w_host = capi.dbl_array(weights, nx)   # read by the call itself, before it returns
-        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
-    if tick_weights is not None:
-        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
-        a.tick_w = tick_weights.data_ptr()
-    res = _alloc_outputs(a, want, {"cost": ("cost", (B,)), "g": ("g", (nx, B)), "H": ("H", (nx, nx, B)),
-                                   "Phi_final": ("Phi_final", (nx, nx, B)), "x_final": ("x_final", (nx, B))}, dtp, state.device)
-    with torch.cuda.device(state.device):
-        capi.check(capi.load().cpmpc_sim_rollout_gn_x0_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
-                                                             _stream_ptr()))
-    return res
-
+    return _gauss_newton_call(capi.SimRolloutGnX0, "cpmpc_sim_rollout_gn_x0_batch", "Phi_final", False, params, dt, state, u,
+                              x_obs, weights, tick_weights, fext, f_base, f_mass, model, want)
 
 def _wrap_pole_angles(d, nx):
     """d [nx, B], a difference of states: its pole angles to the nearest multiple of 2 pi, as the kernels wrap a residual"""
@@ -1296,21 +1289,12 @@ def sim_ekf(params, dt, state, cov, u, y, weights, process_noise=None, tick_weig
     B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
     _require_cuda_tensor(cov, "cov", dtp, (nx, nx, B))
     a.P0 = cov.data_ptr()
-    if y is not None:
-        _require_cuda_tensor(y, "y", dtp, (T, nx, B))
-        a.y = y.data_ptr()
-    w_host = q_host = None   # read by the call itself, before it returns
-    if weights is not None:
-        w_host = capi.dbl_array(weights, nx)
-        a.w_host = C.cast(w_host, C.POINTER(C.c_double))
+    w_host = _window_inputs(a, "y", y, weights, tick_weights, dtp, T, nx, B)
     if y is None and (w_host is None or any(v > 0 for v in w_host)):
         raise ValueError("y (the measurements) is required where a weight is > 0")
     if process_noise is not None:
-        q_host = capi.dbl_array(process_noise, nx)
+        q_host = capi.dbl_array(process_noise, nx)   # read by the call itself, before it returns
         a.q_host = C.cast(q_host, C.POINTER(C.c_double))
-    if tick_weights is not None:
-        _require_cuda_tensor(tick_weights, "tick_weights", dtp, (T, B))
-        a.tick_w = tick_weights.data_ptr()
     res = _alloc_outputs(a, want, {"x_final": ("x_final", (nx, B)), "P_final": ("P_final", (nx, nx, B)),
                                    "xs": ("xs", (T, nx, B)), "nis": ("nis", (B,))}, dtp, state.device)
     with torch.cuda.device(state.device):

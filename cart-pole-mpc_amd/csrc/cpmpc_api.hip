@@ -1025,64 +1025,57 @@ extern "C" int cpmpc_sim_rollout_vjp_batch(int model, int dtype, int64_t B, cons
   });
 }
 
-// ---- the rollout's forward mode and the Gauss-Newton normal equations of a window (sim_rollout_gn_kernels.hpp) ----------
-static int check_sim_rollout_gn_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
-                                     const cpmpc_sim_rollout_gn* a) {
-  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout_gn)");
-  int rc = check_rollout_common("cpmpc_sim_rollout_gn", a->struct_size, sizeof(cpmpc_sim_rollout_gn), a->x0, a->u,
-                                dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+// ---- the window calls on top of the rollout: the two Gauss-Newton fits and the Kalman filter ---------------------------
+// A host vector of n weights or variances, NULL for its default: every entry finite and >= 0
+static int check_host_weights(const char* name, const double* v, size_t n) {
+  if (v)
+    for (size_t q = 0; q < n; ++q)
+      if (!(v[q] >= 0.0) || !std::isfinite(v[q])) return fail(CPMPC_ERR_INVALID_ARG, "%s[%zu] must be finite and >= 0", name, q);
+  return CPMPC_OK;
+}
+
+// The argument checks of the two Gauss-Newton calls (no device needed): their structs `what` differ in the output
+// `final_field`, `final_name` [final_extent][B], and in n_unknowns, the length of g and the order of H
+template <typename Args>
+static int check_sim_rollout_gn_args(const char* what, const Args* a, void* Args::*final_field, const char* final_name,
+                                     size_t final_extent, size_t n_unknowns, int model, int dtype, int64_t B,
+                                     const double* dyn_shared_host, double dt, int T) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (%s)", what);
+  int rc = check_rollout_common(what, a->struct_size, sizeof(Args), a->x0, a->u, dyn_shared_host, a->dyn, dt, T, model, dtype, B);
   if (rc) return rc;
-  if (!a->cost && !a->g && !a->H && !a->S_final && !a->x_final)
+  void* const final_out = a->*final_field;
+  if (!a->cost && !a->g && !a->H && !final_out && !a->x_final)
     return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
   if ((a->cost || a->g || a->H) && !a->x_obs) return fail(CPMPC_ERR_INVALID_ARG, "cost / g / H are given without x_obs");
   const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
-  if (a->w_host)
-    for (size_t q = 0; q < nx; ++q)
-      if (!(a->w_host[q] >= 0.0) || !std::isfinite(a->w_host[q]))
-        return fail(CPMPC_ERR_INVALID_ARG, "w_host[%zu] must be finite and >= 0", q);
-  const ArraySpan outs[5] = {{a->cost, 1, "cost"}, {a->g, np, "g"}, {a->H, np * np, "H"}, {a->S_final, nx * np, "S_final"},
-                             {a->x_final, nx, "x_final"}};
+  rc = check_host_weights("w_host", a->w_host, nx);
+  if (rc) return rc;
+  const ArraySpan outs[5] = {{a->cost, 1, "cost"}, {a->g, n_unknowns, "g"}, {a->H, n_unknowns * n_unknowns, "H"},
+                             {final_out, final_extent, final_name}, {a->x_final, nx, "x_final"}};
   const ArraySpan ins[6] = {{a->x0, nx, "x0"},     {a->u, nt, "u"},
                             {a->fext, 4, "fext"},  {a->dyn, np, "dyn"},
                             {a->x_obs, nt * nx, "x_obs"}, {a->tick_w, nt, "tick_w"}};
   return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }
 
+// the rollout's forward mode in the parameters and the normal equations of their fit (sim_rollout_gn_kernels.hpp)
 extern "C" int cpmpc_sim_rollout_gn_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                           const cpmpc_sim_rollout_gn* a, void* stream) {
-  int rc = check_sim_rollout_gn_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model);
+  int rc = check_sim_rollout_gn_args("cpmpc_sim_rollout_gn", a, &cpmpc_sim_rollout_gn::S_final, "S_final", nx * np, np, model, dtype, B,
+                                     dyn_shared_host, dt, T);
   if (rc) return rc;
   return run_plant_call(dt, false, [&](int n_sub, double h_last) {
     engine_for(dtype, model)->sim_rollout_gn(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
   });
 }
 
-// ---- the rollout's forward mode in the initial state and the normal equations of the fit of x0 (sim_rollout_gn_x0_kernels.hpp)
-static int check_sim_rollout_gn_x0_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
-                                        const cpmpc_sim_rollout_gn_x0* a) {
-  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout_gn_x0)");
-  int rc = check_rollout_common("cpmpc_sim_rollout_gn_x0", a->struct_size, sizeof(cpmpc_sim_rollout_gn_x0), a->x0, a->u,
-                                dyn_shared_host, a->dyn, dt, T, model, dtype, B);
-  if (rc) return rc;
-  if (!a->cost && !a->g && !a->H && !a->Phi_final && !a->x_final)
-    return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
-  if ((a->cost || a->g || a->H) && !a->x_obs) return fail(CPMPC_ERR_INVALID_ARG, "cost / g / H are given without x_obs");
-  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
-  if (a->w_host)
-    for (size_t q = 0; q < nx; ++q)
-      if (!(a->w_host[q] >= 0.0) || !std::isfinite(a->w_host[q]))
-        return fail(CPMPC_ERR_INVALID_ARG, "w_host[%zu] must be finite and >= 0", q);
-  const ArraySpan outs[5] = {{a->cost, 1, "cost"}, {a->g, nx, "g"}, {a->H, nx * nx, "H"}, {a->Phi_final, nx * nx, "Phi_final"},
-                             {a->x_final, nx, "x_final"}};
-  const ArraySpan ins[6] = {{a->x0, nx, "x0"},     {a->u, nt, "u"},
-                            {a->fext, 4, "fext"},  {a->dyn, np, "dyn"},
-                            {a->x_obs, nt * nx, "x_obs"}, {a->tick_w, nt, "tick_w"}};
-  return check_no_overlap(outs, ins, row_bytes(dtype, B));
-}
-
+// the rollout's forward mode in the initial state and the normal equations of the fit of x0 (sim_rollout_gn_x0_kernels.hpp)
 extern "C" int cpmpc_sim_rollout_gn_x0_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                              const cpmpc_sim_rollout_gn_x0* a, void* stream) {
-  int rc = check_sim_rollout_gn_x0_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  const size_t nx = (size_t)model_nx(model);
+  int rc = check_sim_rollout_gn_args("cpmpc_sim_rollout_gn_x0", a, &cpmpc_sim_rollout_gn_x0::Phi_final, "Phi_final", nx * nx, nx, model,
+                                     dtype, B, dyn_shared_host, dt, T);
   if (rc) return rc;
   return run_plant_call(dt, false, [&](int n_sub, double h_last) {
     engine_for(dtype, model)->sim_rollout_gn_x0(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
@@ -1099,14 +1092,11 @@ static int check_sim_ekf_args(int model, int dtype, int64_t B, const double* dyn
   if (!a->P0) return fail(CPMPC_ERR_INVALID_ARG, "null argument (P0)");
   if (!a->x_final && !a->P_final && !a->xs && !a->nis) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
   const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  rc = check_host_weights("w_host", a->w_host, nx);
+  if (!rc) rc = check_host_weights("q_host", a->q_host, nx);
+  if (rc) return rc;
   bool measured = !a->w_host;  // NULL: ones
-  for (size_t i = 0; i < nx; ++i) {
-    if (a->w_host && (!(a->w_host[i] >= 0.0) || !std::isfinite(a->w_host[i])))
-      return fail(CPMPC_ERR_INVALID_ARG, "w_host[%zu] must be finite and >= 0", i);
-    if (a->q_host && (!(a->q_host[i] >= 0.0) || !std::isfinite(a->q_host[i])))
-      return fail(CPMPC_ERR_INVALID_ARG, "q_host[%zu] must be finite and >= 0", i);
-    if (a->w_host && a->w_host[i] > 0.0) measured = true;
-  }
+  for (size_t i = 0; i < nx && !measured; ++i) measured = a->w_host[i] > 0.0;
   if (measured && !a->y) return fail(CPMPC_ERR_INVALID_ARG, "a state is measured (w_host > 0) without y");
   const ArraySpan outs[4] = {{a->x_final, nx, "x_final"}, {a->P_final, nx * nx, "P_final"}, {a->xs, nt * nx, "xs"},
                              {a->nis, 1, "nis"}};

@@ -624,12 +624,19 @@ static void sim_rollout_vjp_impl(int64_t B, const double* dyn_shared_host, int n
   });
 }
 
+// A host vector of per-state weights or variances as the kernels take it; NULL: `dflt` for every state
+template <typename R, int NX>
+static StateWeights<R, NX> state_weights(const double* v, double dflt) {
+  StateWeights<R, NX> sw;
+  for (int q = 0; q < NX; ++q) sw.w[q] = (R)(v ? v[q] : dflt);
+  return sw;
+}
+
 // ---- the rollout's forward mode with the normal equations of the window, one launch (sim_rollout_gn_kernels.hpp) -------
 template <typename R, typename M>
 static void sim_rollout_gn_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                                 const cpmpc_sim_rollout_gn* a, hipStream_t stream) {
-  StateWeights<R, M::NX> sw;
-  for (int q = 0; q < M::NX; ++q) sw.w[q] = a->w_host ? (R)a->w_host[q] : R(1);
+  const StateWeights<R, M::NX> sw = state_weights<R, M::NX>(a->w_host, 1.0);
   with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
     constexpr bool PL = decltype(per_lane)::value;
     const SharedPlantParams<R, M> sp = shared_plant_params<R, M, PL>(dyn_shared_host);
@@ -644,8 +651,7 @@ static void sim_rollout_gn_impl(int64_t B, const double* dyn_shared_host, int n_
 template <typename R, typename M>
 static void sim_rollout_gn_x0_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                                    const cpmpc_sim_rollout_gn_x0* a, hipStream_t stream) {
-  StateWeights<R, M::NX> sw;
-  for (int q = 0; q < M::NX; ++q) sw.w[q] = a->w_host ? (R)a->w_host[q] : R(1);
+  const StateWeights<R, M::NX> sw = state_weights<R, M::NX>(a->w_host, 1.0);
   with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
     constexpr bool PL = decltype(per_lane)::value;
     hipLaunchKernelGGL((sim_rollout_gn_x0_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
@@ -659,11 +665,7 @@ static void sim_rollout_gn_x0_impl(int64_t B, const double* dyn_shared_host, int
 template <typename R, typename M>
 static void sim_ekf_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_ekf* a,
                          hipStream_t stream) {
-  StateWeights<R, M::NX> sw, q;
-  for (int i = 0; i < M::NX; ++i) {
-    sw.w[i] = a->w_host ? (R)a->w_host[i] : R(1);
-    q.w[i] = a->q_host ? (R)a->q_host[i] : R(0);
-  }
+  const StateWeights<R, M::NX> sw = state_weights<R, M::NX>(a->w_host, 1.0), q = state_weights<R, M::NX>(a->q_host, 0.0);
   with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
     constexpr bool PL = decltype(per_lane)::value;
     hipLaunchKernelGGL((sim_ekf_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,

@@ -12,10 +12,11 @@
 // A tick's prediction is sim_jac_tick.inc's sub-step loop -- rk4_step_jac_m, step_jac_apply a column at a time, Phi from I,
 // the closed-form columns (models.hpp: trivial_cols) closed-form -- without gamma, and with the STATE advanced by
 // plant_sub_step, the function sim_rollout_kernel's loop calls, from the same point: the predicted state is that kernel's bit
-// for bit (see the loop).  The kernel keeps its own loop for that, as sim_rollout_gn_x0_kernel does.  The tick's A stays in
+// for bit (see the loop).  The `for` statement is the kernel's own, as sim_rollout_gn_x0_kernel's is; Phi = I (phi_identity) and
+// Phi <- A Phi (sim_phi_step.inc) are the pieces of sim_jac_tick.inc, and P_final leaves by sim_store_sym.inc.  The tick's A stays in
 // registers and never goes to memory.  The products A P and (A P) A^T take the closed-form columns' entries as the 0, 1 and
 // t_sum they are: a structural zero is not multiplied, a one is not a product.  Only the lower triangle of P is computed and
-// kept, (j, k <= j) at j (j + 1) / 2 + k.
+// kept, (j, k <= j) at tri(j, k) (sim_window.hpp).
 //
 // One problem per lane, no barrier.  P lives in lane-private LDS, acc[field][threadIdx.x], while the sub-step loop runs, so
 // what is live there is sim_rollout_gn_x0_kernel's set: the tick's Phi and the sub-step's A.  Everything is computed
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
                                                       R* x_final, R* P_final, R* xs_out, R* nis) {
   constexpr int NX = M::NX, NQ = M::NQ;
   constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);  // sim_jac_kernel's closed-form columns
-  constexpr int NH = NX * (NX + 1) / 2;  // P's lower triangle
+  constexpr int NH = tri(NX, 0);  // P's lower triangle, (j, k <= j) at tri(j, k)
   __shared__ R acc[NH][64];
   const int lane = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
 #pragma unroll
   for (int j = 0; j < NX; ++j)
 #pragma unroll
-    for (int kk = 0; kk <= j; ++kk) acc[j * (j + 1) / 2 + kk][lane] = P0[(j * NX + kk) * B + p];
+    for (int kk = 0; kk <= j; ++kk) acc[tri(j, kk)][lane] = P0[(j * NX + kk) * B + p];
   R nis_sum = R(0);
 
 #pragma unroll 1
@@ -75,11 +76,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
     const R uu = u[(int64_t)t * B + p];
     // ---- predict: the tick's sub-step loop, Phi from I
     R Phi[NX][NX];
-#pragma unroll
-    for (int r = 0; r < NX; ++r)
-#pragma unroll
-      for (int c = 0; c < NX; ++c)
-        if (!((TRIV >> c) & 1u)) Phi[r][c] = (r == c) ? R(1) : R(0);
+    phi_identity<R, M>(Phi);
     R t_sum = R(0);  // entry (c - NQ, c) of a trivial velocity column: the sub-steps' lengths of this tick
     {
       const R internal_dt = R(0.001);
@@ -100,21 +97,12 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
         }
         plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain_x);
         rk4_step_jac_m<R, M, true>(k, h, xj, uu, fe, A, Bv, chain);
-#pragma unroll
-        for (int c = 0; c < NX; ++c) {
-          if ((TRIV >> c) & 1u) continue;
-          R v[NX], yv[NX];
-#pragma unroll
-          for (int m = 0; m < NX; ++m) v[m] = Phi[m][c];
-          step_jac_apply<R, M>(A, h, v, yv);
-#pragma unroll
-          for (int r = 0; r < NX; ++r) Phi[r][c] = yv[r];
-        }
+#include "sim_phi_step.inc"
         if (TRIV != 0u) t_sum += h;
       }
     }
 
-    // ---- P- = A P A^T + diag(q), a row of A P at a time; P is (j, k) -> Pm[max (max + 1) / 2 + min]
+    // ---- P- = A P A^T + diag(q), a row of A P at a time; P is (j, k) -> Pm[tri_sym(j, k)]
     R Pm[NH], Pn[NH];
 #pragma unroll
     for (int f = 0; f < NH; ++f) Pm[f] = acc[f][lane];
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
         R s = R(0);
 #pragma unroll
         for (int l = 0; l < NX; ++l)
-          ekf_add_term<R, NX, NQ, TRIV>(Phi, t_sum, j, l, Pm[l >= c ? l * (l + 1) / 2 + c : c * (c + 1) / 2 + l], have, s);
+          ekf_add_term<R, NX, NQ, TRIV>(Phi, t_sum, j, l, Pm[tri_sym(l, c)], have, s);
         row[c] = s;
       }
 #pragma unroll
@@ -136,7 +124,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
         R s = R(0);
 #pragma unroll
         for (int l = 0; l < NX; ++l) ekf_add_term<R, NX, NQ, TRIV>(Phi, t_sum, kk, l, row[l], have, s);
-        Pn[j * (j + 1) / 2 + kk] = (kk == j) ? s + q.w[j] : s;
+        Pn[tri(j, kk)] = (kk == j) ? s + q.w[j] : s;
       }
     }
 
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
       const R rho = om * sw.w[i];
       if (rho > R(0)) {
         const R rv = R(1) / rho;
-        const R s = Pn[i * (i + 1) / 2 + i] + rv;
+        const R s = Pn[tri(i, i)] + rv;
         R res[NX];
 #pragma unroll
         for (int m = 0; m < NX; ++m) res[m] = R(0);
@@ -157,7 +145,7 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
         const R nu = res[i];
         R gain[NX];
 #pragma unroll
-        for (int j = 0; j < NX; ++j) gain[j] = Pn[j >= i ? j * (j + 1) / 2 + i : i * (i + 1) / 2 + j] / s;
+        for (int j = 0; j < NX; ++j) gain[j] = Pn[tri_sym(j, i)] / s;
 #pragma unroll
         for (int j = 0; j < NX; ++j) xs[j] += gain[j] * nu;
         nis_sum += nu * nu / s;
@@ -167,11 +155,11 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
 #pragma unroll
           for (int kk = 0; kk <= j; ++kk) {
             if (kk == i) continue;
-            Pn[j * (j + 1) / 2 + kk] -= gain[j] * Pn[kk >= i ? kk * (kk + 1) / 2 + i : i * (i + 1) / 2 + kk];
+            Pn[tri(j, kk)] -= gain[j] * Pn[tri_sym(kk, i)];
           }
         }
 #pragma unroll
-        for (int j = 0; j < NX; ++j) Pn[j >= i ? j * (j + 1) / 2 + i : i * (i + 1) / 2 + j] = gain[j] * rv;
+        for (int j = 0; j < NX; ++j) Pn[tri_sym(j, i)] = gain[j] * rv;
         acted = true;
       }
     }
@@ -187,15 +175,11 @@ __global__ __launch_bounds__(64) void sim_ekf_kernel(int64_t B, typename PlantCo
   if (x_final)
 #pragma unroll
     for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
-  if (P_final)
-#pragma unroll
-    for (int j = 0; j < NX; ++j)
-#pragma unroll
-      for (int kk = 0; kk <= j; ++kk) {
-        const R v = acc[j * (j + 1) / 2 + kk][lane];
-        P_final[(j * NX + kk) * B + p] = v;
-        if (kk != j) P_final[(kk * NX + j) * B + p] = v;
-      }
+  if (P_final) {
+    constexpr int NS = NX;
+    R* const out = P_final;
+#include "sim_store_sym.inc"
+  }
   if (nis) nis[p] = nis_sum;
 }
 

@@ -12,7 +12,7 @@
 // gx = Phi^T gbar [NX][B] and gu = gamma . gbar [B] contracted in registers.  Derivatives with respect to the state and the
 // control only: the dynamics parameters have sim_param_kernels.hpp; none for the external forces or the step length.
 #pragma once
-#include "mpc_kernels.hpp"
+#include "sim_window.hpp"
 
 namespace cpmpc {
 
@@ -45,12 +45,7 @@ __global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename PlantCo
 #pragma unroll
     for (int r = 0; r < NX; ++r)
 #pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R v;
-        if ((TRIV >> c) & 1u) v = (r == c) ? R(1) : ((c >= NQ && r == c - NQ) ? t_sum : R(0));  // the closed-form columns
-        else v = Phi[r][c];
-        A_out[(r * NX + c) * B + p] = v;
-      }
+      for (int c = 0; c < NX; ++c) A_out[(r * NX + c) * B + p] = phi_entry<R, M>(Phi, t_sum, r, c);
   if (Bu)
 #pragma unroll
     for (int r = 0; r < NX; ++r) Bu[r * B + p] = gam[r];

@@ -15,35 +15,16 @@
 // lane-private LDS, acc[field][threadIdx.x], read and written once per tick and never by another lane: no barrier anywhere.
 // In registers they put three of the eight instantiations into scratch.  S never goes to memory except as
 // S_final.  The accumulation runs where any of cost, g, H is asked for (a wave-uniform choice) and is the same statements
-// whichever of them are stored, so each is bitwise the same whatever else is asked for.
+// whichever of them are stored, so each is bitwise the same whatever else is asked for.  The tick's residual, its share of
+// the normal equations and the store of H are the texts sim_rollout_gn_x0_kernel includes too: sim_window_residual.inc,
+// sim_normal_eq.inc (here with dense columns, NeverZero) and sim_store_sym.inc.
 // n_sub == 0 is the identity map: S stays 0, so H = 0, g = 0, S_final = 0, x_final = x0, and cost is the weighted residual of
 // x0 against every x_obs[t].  Not differentiated: the external forces, dt and x0; the wrap has unit derivative.
 #pragma once
 #include "sim_param_kernels.hpp"
+#include "sim_window.hpp"
 
 namespace cpmpc {
-
-// the residual weights of the states, in the kernel's scalar type
-template <typename R, int NX>
-struct StateWeights {
-  R w[NX];
-};
-
-// The pole angles of a residual to [-pi, pi], by the NEAREST multiple of 2 pi: a residual inside that range, which is every one
-// of a sensible fit, comes back bit for bit.  (wrap_angles sends a small negative angle through + 2 pi - 2 pi, which costs a
-// residual of 0.05 rad five of a float's digits: mod_pi is made for angles, where an error of eps pi is the format's own.)
-template <typename R, typename M>
-__device__ __forceinline__ void wrap_residual(R (&r)[M::NX]) {
-  constexpr R two_pi = static_cast<R>(2 * 3.14159265358979323846);
-  constexpr R inv_two_pi = static_cast<R>(0.15915494309189533577);
-#pragma unroll
-  for (int t = 1; t < M::NQ; ++t) {
-    R n;
-    if constexpr (sizeof(R) == 4) n = __builtin_rintf(r[t] * inv_two_pi);
-    else n = __builtin_rint(r[t] * inv_two_pi);
-    r[t] = Math<R>::fma(-n, two_pi, r[t]);
-  }
-}
 
 // Outputs, each written only where its pointer is given: cost [B]; g [NP][B]; H [NP*NP][B], full, (j, k) and (k, j) from the one
 // accumulated value; S_final [NX*NP][B], element (r, j) at field r*NP + j as P; x_final [NX][B].  x_obs [T][NX][B] is read only
@@ -55,7 +36,7 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_kernel(int64_t B, typename 
                                                              StateWeights<R, M::NX> sw, const R* tick_w, R* cost, R* g, R* H,
                                                              R* S_final, R* x_final) {
   constexpr int NX = M::NX, NP = M::NP;
-  constexpr int NH = NP * (NP + 1) / 2;  // H's lower triangle, (j, k <= j) at j (j + 1) / 2 + k; g behind it
+  constexpr int NH = tri(NP, 0);  // H's lower triangle, (j, k <= j) at tri(j, k); g behind it
   __shared__ R acc[NH + NP][64];
   const int lane = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,35 +74,11 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_kernel(int64_t B, typename 
       }
     }
     if (fit) {
-      R res[NX];
-#pragma unroll
-      for (int q = 0; q < NX; ++q) res[q] = x_obs[((int64_t)t * NX + q) * B + p] - xs[q];
-      wrap_residual<R, M>(res);
-      const R om = tick_w ? tick_w[(int64_t)t * B + p] : R(1);
-      R wr[NX];  // W r
-#pragma unroll
-      for (int q = 0; q < NX; ++q) wr[q] = sw.w[q] * res[q];
-      R c = wr[0] * res[0];
-#pragma unroll
-      for (int q = 1; q < NX; ++q) c += wr[q] * res[q];
-      cost_sum += (R(0.5) * om) * c;
-#pragma unroll
-      for (int j = 0; j < NP; ++j) {
-        R ws[NX];  // om W S[j]
-#pragma unroll
-        for (int q = 0; q < NX; ++q) ws[q] = om * (sw.w[q] * S[j][q]);
-        R gj = ws[0] * res[0];
-#pragma unroll
-        for (int q = 1; q < NX; ++q) gj += ws[q] * res[q];
-        acc[NH + j][lane] -= gj;
-#pragma unroll
-        for (int kk = 0; kk <= j; ++kk) {
-          R h = ws[0] * S[kk][0];
-#pragma unroll
-          for (int q = 1; q < NX; ++q) h += ws[q] * S[kk][q];
-          acc[j * (j + 1) / 2 + kk][lane] += h;
-        }
-      }
+#include "sim_window_residual.inc"  // res, om; adds to cost_sum
+      constexpr int NC = NP;
+      const R (&col)[NP][NX] = S;  // the columns, under the names sim_normal_eq.inc reads
+      using Zero = NeverZero;
+#include "sim_normal_eq.inc"
     }
   }
 
@@ -129,15 +86,11 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_kernel(int64_t B, typename 
   if (g)
 #pragma unroll
     for (int j = 0; j < NP; ++j) g[j * B + p] = acc[NH + j][lane];
-  if (H)
-#pragma unroll
-    for (int j = 0; j < NP; ++j)
-#pragma unroll
-      for (int kk = 0; kk <= j; ++kk) {
-        const R h = acc[j * (j + 1) / 2 + kk][lane];
-        H[(j * NP + kk) * B + p] = h;
-        if (kk != j) H[(kk * NP + j) * B + p] = h;
-      }
+  if (H) {
+    constexpr int NS = NP;
+    R* const out = H;
+#include "sim_store_sym.inc"
+  }
   if (S_final)
 #pragma unroll
     for (int j = 0; j < NP; ++j)

@@ -7,9 +7,10 @@
 //     g       = -sum_t om_t Phi_{t+1}^T W r_t       = dcost/dx0
 //     H       =  sum_t om_t Phi_{t+1}^T W Phi_{t+1} the Gauss-Newton matrix; the step is -H^-1 g
 // A tick is sim_jac_tick.inc's sub-step loop -- rk4_step_jac_m, wrap_angles, step_jac_apply a column at a time -- with Phi
-// carried over the tick boundary instead of starting from I, and without gamma.  The kernel keeps its own loop for that, as
-// sim_rollout_gn_kernel keeps its own beside sim_param_tick.inc.  No per-tick A_t is formed and Phi never goes to memory
-// except as Phi_final.
+// carried over the tick boundary instead of starting from I, and without gamma.  The `for` statement is the kernel's own; what
+// it does to Phi is not: phi_identity and phi_entry (sim_window.hpp) and the text sim_phi_step.inc are the ones sim_jac_tick.inc
+// and sim_jac_kernel use, so Phi_final of one tick is that kernel's A by construction.  No per-tick A_t is formed and Phi never
+// goes to memory except as Phi_final.
 //
 // The closed-form columns (models.hpp: trivial_cols) stay closed-form across ticks, because their pattern is closed under the
 // product: a position column stays e_c, a velocity column stays e_c + t_sum e_{c-NQ} with t_sum the sub-steps' lengths added
@@ -18,7 +19,8 @@
 //
 // One problem per lane.  Phi, x, t_sum and cost stay in registers over the ticks; H (packed lower triangle) and g live in
 // lane-private LDS, acc[field][threadIdx.x], read and written once per tick and never by another lane: no barrier anywhere
-// (the layout of sim_rollout_gn_kernel).  The accumulation runs where any of cost, g, H is asked for (a wave-uniform
+// (the layout of sim_rollout_gn_kernel, and its texts: sim_window_residual.inc, sim_normal_eq.inc -- here with PhiZero, the
+// structural zeros of the closed-form columns -- and sim_store_sym.inc).  The accumulation runs where any of cost, g, H is asked for (a wave-uniform
 // choice) and is the same statements whichever of them are stored, so each is bitwise the same whatever else is asked for.
 // n_sub == 0 is the identity map: Phi stays I and x_final = x0; H = sum_t om_t W and g = -sum_t om_t W r_t come from the
 // same statements.  Not differentiated: the parameters (sim_rollout_gn_kernel), the external forces and dt; the wrap has
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_x0_kernel(int64_t B, typena
                                                                 R* H, R* Phi_final, R* x_final) {
   constexpr int NX = M::NX, NQ = M::NQ;
   constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);  // sim_jac_kernel's closed-form columns
-  constexpr int NH = NX * (NX + 1) / 2;  // H's lower triangle, (j, k <= j) at j (j + 1) / 2 + k; g behind it
+  constexpr int NH = tri(NX, 0);  // H's lower triangle, (j, k <= j) at tri(j, k); g behind it
   __shared__ R acc[NH + NX][64];
   const int lane = threadIdx.x;
   const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -52,11 +54,7 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_x0_kernel(int64_t B, typena
   R xs[NX], Phi[NX][NX];
 #pragma unroll
   for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
-#pragma unroll
-  for (int r = 0; r < NX; ++r)
-#pragma unroll
-    for (int c = 0; c < NX; ++c)
-      if (!((TRIV >> c) & 1u)) Phi[r][c] = (r == c) ? R(1) : R(0);
+  phi_identity<R, M>(Phi);
 #pragma unroll
   for (int f = 0; f < NH + NX; ++f) acc[f][lane] = R(0);
   R t_sum = R(0);  // entry (c - NQ, c) of a trivial velocity column: the sub-steps' lengths of every tick so far
@@ -74,32 +72,12 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_x0_kernel(int64_t B, typena
         R A[NX][NX], Bv[NX];
         rk4_step_jac_m<R, M, true>(k, h, xs, uu, fe, A, Bv, chain);
         wrap_angles<R, M>(xs);
-#pragma unroll
-        for (int c = 0; c < NX; ++c) {
-          if ((TRIV >> c) & 1u) continue;
-          R v[NX], y[NX];
-#pragma unroll
-          for (int m = 0; m < NX; ++m) v[m] = Phi[m][c];
-          step_jac_apply<R, M>(A, h, v, y);  // Phi is carried, not reset
-#pragma unroll
-          for (int r = 0; r < NX; ++r) Phi[r][c] = y[r];
-        }
+#include "sim_phi_step.inc"  // Phi is carried, not reset
         if (TRIV != 0u) t_sum += h;
       }
     }
     if (fit) {
-      R res[NX];
-#pragma unroll
-      for (int q = 0; q < NX; ++q) res[q] = x_obs[((int64_t)t * NX + q) * B + p] - xs[q];
-      wrap_residual<R, M>(res);
-      const R om = tick_w ? tick_w[(int64_t)t * B + p] : R(1);
-      R wr[NX];  // W r
-#pragma unroll
-      for (int q = 0; q < NX; ++q) wr[q] = sw.w[q] * res[q];
-      R c = wr[0] * res[0];
-#pragma unroll
-      for (int q = 1; q < NX; ++q) c += wr[q] * res[q];
-      cost_sum += (R(0.5) * om) * c;
+#include "sim_window_residual.inc"  // res, om; adds to cost_sum
       R col[NX][NX];  // col[j][q] = Phi(q, j), the closed-form columns as they are known; structural zeros are never read
 #pragma unroll
       for (int j = 0; j < NX; ++j)
@@ -109,36 +87,9 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_x0_kernel(int64_t B, typena
           if ((TRIV >> j) & 1u) col[j][q] = (q == j) ? R(1) : t_sum;
           else col[j][q] = Phi[q][j];
         }
-#pragma unroll
-      for (int j = 0; j < NX; ++j) {
-        R ws[NX];  // om W Phi[:, j]
-#pragma unroll
-        for (int q = 0; q < NX; ++q)
-          if (!struct_zero<NX, NQ>(TRIV, q, j)) ws[q] = om * (sw.w[q] * col[j][q]);
-        {
-          bool have = false;
-          R gj = R(0);
-#pragma unroll
-          for (int q = 0; q < NX; ++q) {
-            if (struct_zero<NX, NQ>(TRIV, q, j)) continue;
-            gj = have ? gj + ws[q] * res[q] : ws[q] * res[q];
-            have = true;
-          }
-          acc[NH + j][lane] -= gj;
-        }
-#pragma unroll
-        for (int kk = 0; kk <= j; ++kk) {
-          bool have = false;
-          R h = R(0);
-#pragma unroll
-          for (int q = 0; q < NX; ++q) {
-            if (struct_zero<NX, NQ>(TRIV, q, j) || struct_zero<NX, NQ>(TRIV, q, kk)) continue;
-            h = have ? h + ws[q] * col[kk][q] : ws[q] * col[kk][q];
-            have = true;
-          }
-          if (have) acc[j * (j + 1) / 2 + kk][lane] += h;  // no common row: an exact zero stays the zero it was set to
-        }
-      }
+      constexpr int NC = NX;
+      using Zero = PhiZero<NX, NQ, TRIV>;
+#include "sim_normal_eq.inc"
     }
   }
 
@@ -146,25 +97,16 @@ __global__ __launch_bounds__(64) void sim_rollout_gn_x0_kernel(int64_t B, typena
   if (g)
 #pragma unroll
     for (int j = 0; j < NX; ++j) g[j * B + p] = acc[NH + j][lane];
-  if (H)
-#pragma unroll
-    for (int j = 0; j < NX; ++j)
-#pragma unroll
-      for (int kk = 0; kk <= j; ++kk) {
-        const R h = acc[j * (j + 1) / 2 + kk][lane];
-        H[(j * NX + kk) * B + p] = h;
-        if (kk != j) H[(kk * NX + j) * B + p] = h;
-      }
+  if (H) {
+    constexpr int NS = NX;
+    R* const out = H;
+#include "sim_store_sym.inc"
+  }
   if (Phi_final)
 #pragma unroll
     for (int r = 0; r < NX; ++r)
 #pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R v;
-        if ((TRIV >> c) & 1u) v = (r == c) ? R(1) : ((c >= NQ && r == c - NQ) ? t_sum : R(0));  // the closed-form columns
-        else v = Phi[r][c];
-        Phi_final[(r * NX + c) * B + p] = v;
-      }
+      for (int c = 0; c < NX; ++c) Phi_final[(r * NX + c) * B + p] = phi_entry<R, M>(Phi, t_sum, r, c);
   if (x_final)
 #pragma unroll
     for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
