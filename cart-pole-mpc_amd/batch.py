@@ -1302,6 +1302,75 @@ def sim_ekf(params, dt, state, cov, u, y, weights, process_noise=None, tick_weig
     return res
 
 
+_RTS_OUTPUTS = ("xs_smooth", "Ps_smooth", "x0_smooth", "P0_smooth", "ok", "x_final", "P_final", "xs", "nis")
+
+
+def _sim_rts_work_rows(model, ticks):
+    """Rows of B numbers of sim_rts's workspace for `ticks` ticks, from the library's own cpmpc_sim_rts_work_rows (44 a tick for
+    the 4-state model and 90 for the 6-state model): the record's layout is written down in one place."""
+    m, _, _ = _model_dims(model)
+    return int(capi.load().cpmpc_sim_rts_work_rows(m, int(ticks)))
+
+
+def sim_rts(params, dt, state, cov, u, y, weights, process_noise=None, tick_weights=None, fext=None, f_base=(0.0, 0.0),
+            f_mass=(0.0, 0.0), model="single", want=("xs_smooth", "x0_smooth", "P0_smooth"), work=None):
+    """The Rauch-Tung-Striebel smoother of B plants over the T ticks of u [T, B], in TWO launches (include/cpmpc.h:
+    cpmpc_sim_rts_batch): every state of the window given ALL of the window's measurements, with its covariance.  Forward it
+    is sim_ekf on the same arguments, unchanged; index 0 is `state` / `cov` and index t is after tick t.  Backward from
+    x^s_T = x_T, P^s_T = P_T, for t = T-1 .. 0, with x-, P- the prediction of tick t and A its Jacobian,
+        G = P_t A^T (P-)^-1,   x^s_t = x_t + G wrap(x^s_{t+1} - x-),   P^s_t = P_t + G (P^s_{t+1} - P-) G^T.
+    No inverse is formed (the Cholesky factor of the diagonally scaled P-, per lane in registers).  A tick whose P- is not
+    positive definite (a pivot of the scaled matrix at or below 8 nx eps: sim_estimate_state's floor) takes G = 0: index t's
+    smoothed values are its filtered ones, the recursion goes on from them and the lane's "ok" is 0 -- the answer for
+    cov = 0, "the start is known".
+
+    Returns a dict with the entries named in `want`,
+        "xs_smooth" [T + 1, nx, B]      the smoothed states, index T is the filtered x_final,
+        "Ps_smooth" [T + 1, nx, nx, B]  their covariances, exactly symmetric, index T is P_final,
+        "x0_smooth" [nx, B], "P0_smooth" [nx, nx, B]   index 0 alone: the window's first state given the whole window,
+        "ok"        [B] int32           1 where every tick's P- was positive definite,
+        "x_final", "P_final", "xs", "nis"   sim_ekf's, bit for bit.
+    Each is bitwise the same whichever others are asked for.
+
+    THE WORKSPACE: the forward pass stores per tick what the backward pass reads -- the predicted state and covariance, the
+    rows of A P, the filtered state and covariance: cpmpc_sim_rts_work_rows(model, T) rows of B numbers, 44 T for the 4-state and
+    90 T for the 6-state model.  At B = 262 144, T = 100, 6-state fp64 that is 18.9 GB; at B = 4096 it is 0.29 GB.
+    work=None allocates it for the call; a caller's contiguous tensor of `state`'s dtype with at least that many numbers
+    per lane, [rows, B], is used instead and holds nothing of meaning afterwards.  The other arguments as sim_ekf's."""
+    want = _want_tuple(want, _RTS_OUTPUTS)
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimRts(struct_size=C.sizeof(capi.SimRts))
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    _require_cuda_tensor(cov, "cov", dtp, (nx, nx, B))
+    a.P0 = cov.data_ptr()
+    w_host = _window_inputs(a, "y", y, weights, tick_weights, dtp, T, nx, B)
+    if y is None and (w_host is None or any(v > 0 for v in w_host)):
+        raise ValueError("y (the measurements) is required where a weight is > 0")
+    if process_noise is not None:
+        q_host = capi.dbl_array(process_noise, nx)   # read by the call itself, before it returns
+        a.q_host = C.cast(q_host, C.POINTER(C.c_double))
+    rows = _sim_rts_work_rows(model, T)
+    if work is None:
+        work = torch.empty((rows, B), dtype=dtp, device=state.device)
+    else:
+        _require_cuda_tensor(work, "work", dtp)
+        if work.dim() != 2 or work.shape[1] != B or work.shape[0] < rows:
+            raise ValueError("work must be [rows, B] with rows >= %d (cpmpc_sim_rts_work_rows), got %s" % (rows, tuple(work.shape)))
+    a.work, a.work_rows = work.data_ptr(), int(work.shape[0])
+    res = _alloc_outputs(a, [w for w in want if w != "ok"],
+                         {"xs_smooth": ("xs_smooth", (T + 1, nx, B)), "Ps_smooth": ("Ps_smooth", (T + 1, nx, nx, B)),
+                          "x0_smooth": ("x0_smooth", (nx, B)), "P0_smooth": ("P0_smooth", (nx, nx, B)),
+                          "x_final": ("x_final", (nx, B)), "P_final": ("P_final", (nx, nx, B)),
+                          "xs": ("xs", (T, nx, B)), "nis": ("nis", (B,))}, dtp, state.device)
+    if "ok" in want:
+        res["ok"] = torch.empty((B,), dtype=torch.int32, device=state.device)
+        a.ok = res["ok"].data_ptr()
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_rts_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a), _stream_ptr()))
+    return {name: res[name] for name in want}
+
+
 def _full_covariance(cov, nx, batch, dtype, name):
     """cov [nx, B] (a diagonal) or [nx, nx, B] -> a fresh [nx, nx, B] tensor"""
     _require_cuda_tensor(cov, name, dtype)
@@ -1453,6 +1522,16 @@ class WindowEstimator:
             raise ValueError("WindowEstimator: no tick has been pushed yet")
         n = self.count
         return self.x0, self.u[:n], self.y[:n], self.w[:n]
+
+    def smooth(self, want=("xs_smooth", "x0_smooth", "P0_smooth"), work=None):
+        """sim_rts over the ticks held, from the rolling prior's mean and covariance: the smoothed states of the window in
+        two launches (sim_rts's dict for `want`).  Needs prior_cov (ValueError without); changes nothing the estimator
+        holds."""
+        if self.prior_cov is None:
+            raise ValueError("WindowEstimator.smooth needs the rolling prior: give prior_cov to the constructor")
+        _, u, y, w = self.held()
+        return sim_rts(self.params, self.dt, self.prior_mean, self.prior_cov, u, y, self.weights,
+                       process_noise=self.process_noise, tick_weights=w, model=self.model, want=want, work=work, **self.forces)
 
     def estimate(self, iterations=2, damping=0.0, prior=None, prior_info=None, want_result=False):
         """sim_estimate_state over the ticks held, from the warm start, with the rolling prior as the arrival cost where

@@ -51,7 +51,7 @@ SYMBOLS = [
     "cpmpc_sim_step_jac_batch", "cpmpc_sim_step_jac_batch_host",
     "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
     "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch", "cpmpc_sim_rollout_gn_batch",
-    "cpmpc_sim_rollout_gn_x0_batch", "cpmpc_sim_ekf_batch",
+    "cpmpc_sim_rollout_gn_x0_batch", "cpmpc_sim_ekf_batch", "cpmpc_sim_rts_batch", "cpmpc_sim_rts_work_rows",
 ]
 
 
@@ -354,6 +354,36 @@ class SimEkf(C.Structure):
     ]
 
 
+class SimRts(C.Structure):
+    """cpmpc_sim_rts: device pointers of cpmpc_sim_rts_batch; the inputs of cpmpc_sim_ekf with the same meaning, the workspace
+    work of work_rows >= cpmpc_sim_rts_work_rows(model, T) rows of B numbers, the filter's nullable outputs x_final, P_final, xs
+    and nis, and the smoother's: xs_smooth, Ps_smooth (T + 1 indices), x0_smooth, P0_smooth (index 0 alone) and ok [B] int32."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("P0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("y", C.c_void_p),
+        ("tick_w", C.c_void_p),
+        ("w_host", C.POINTER(C.c_double)),
+        ("q_host", C.POINTER(C.c_double)),
+        ("work", C.c_void_p),
+        ("work_rows", C.c_int64),
+        ("x_final", C.c_void_p),
+        ("P_final", C.c_void_p),
+        ("xs", C.c_void_p),
+        ("nis", C.c_void_p),
+        ("xs_smooth", C.c_void_p),
+        ("Ps_smooth", C.c_void_p),
+        ("x0_smooth", C.c_void_p),
+        ("P0_smooth", C.c_void_p),
+        ("ok", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -489,6 +519,9 @@ def load():
     L.cpmpc_sim_rollout_gn_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutGn), vp]
     L.cpmpc_sim_rollout_gn_x0_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutGnX0), vp]
     L.cpmpc_sim_ekf_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimEkf), vp]
+    L.cpmpc_sim_rts_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRts), vp]
+    L.cpmpc_sim_rts_work_rows.argtypes = [i32, i32]
+    L.cpmpc_sim_rts_work_rows.restype = i64
     _lib = L
     return L
 

@@ -1082,22 +1082,33 @@ extern "C" int cpmpc_sim_rollout_gn_x0_batch(int model, int dtype, int64_t B, co
   });
 }
 
-// ---- the extended Kalman filter over T ticks (sim_ekf_kernels.hpp) ------------------------------------------------------
-static int check_sim_ekf_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
-                              const cpmpc_sim_ekf* a) {
-  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_ekf)");
-  int rc = check_rollout_common("cpmpc_sim_ekf", a->struct_size, sizeof(cpmpc_sim_ekf), a->x0, a->u, dyn_shared_host, a->dyn,
-                                dt, T, model, dtype, B);
+// ---- the extended Kalman filter over T ticks (sim_ekf_kernels.hpp) and the smoother behind it (sim_rts_kernels.hpp) -------
+// What the filter's and the smoother's structs `what` are checked for alike (no device needed): the rollout's rules, P0, an
+// output, the host vectors, and y where a state is measured
+template <typename Args>
+static int check_ekf_inputs(const char* what, const Args* a, bool any_output, int model, int dtype, int64_t B,
+                            const double* dyn_shared_host, double dt, int T) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (%s)", what);
+  int rc = check_rollout_common(what, a->struct_size, sizeof(Args), a->x0, a->u, dyn_shared_host, a->dyn, dt, T, model, dtype, B);
   if (rc) return rc;
   if (!a->P0) return fail(CPMPC_ERR_INVALID_ARG, "null argument (P0)");
-  if (!a->x_final && !a->P_final && !a->xs && !a->nis) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
-  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  if (!any_output) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  const size_t nx = (size_t)model_nx(model);
   rc = check_host_weights("w_host", a->w_host, nx);
   if (!rc) rc = check_host_weights("q_host", a->q_host, nx);
   if (rc) return rc;
   bool measured = !a->w_host;  // NULL: ones
   for (size_t i = 0; i < nx && !measured; ++i) measured = a->w_host[i] > 0.0;
   if (measured && !a->y) return fail(CPMPC_ERR_INVALID_ARG, "a state is measured (w_host > 0) without y");
+  return CPMPC_OK;
+}
+
+static int check_sim_ekf_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                              const cpmpc_sim_ekf* a) {
+  int rc = check_ekf_inputs("cpmpc_sim_ekf", a, a && (a->x_final || a->P_final || a->xs || a->nis), model, dtype, B,
+                            dyn_shared_host, dt, T);
+  if (rc) return rc;
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
   const ArraySpan outs[4] = {{a->x_final, nx, "x_final"}, {a->P_final, nx * nx, "P_final"}, {a->xs, nt * nx, "xs"},
                              {a->nis, 1, "nis"}};
   const ArraySpan ins[7] = {{a->x0, nx, "x0"},      {a->P0, nx * nx, "P0"}, {a->u, nt, "u"},          {a->fext, 4, "fext"},
@@ -1111,6 +1122,58 @@ extern "C" int cpmpc_sim_ekf_batch(int model, int dtype, int64_t B, const double
   if (rc) return rc;
   return run_plant_call(dt, false, [&](int n_sub, double h_last) {
     engine_for(dtype, model)->sim_ekf(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
+// rows of B numbers the smoother's forward pass records: T (2 NX + 2 NH + NX^2) (sim_window.hpp: RtsRecord)
+extern "C" int64_t cpmpc_sim_rts_work_rows(int model, int T) {
+  if ((model != CPMPC_MODEL_SINGLE && model != CPMPC_MODEL_DOUBLE) || T < 1) return 0;
+  const int64_t nx = model_nx(model);
+  return (int64_t)T * (2 * nx + nx * (nx + 1) + nx * nx);
+}
+
+static int check_sim_rts_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                              const cpmpc_sim_rts* a) {
+  const bool any = a && (a->x_final || a->P_final || a->xs || a->nis || a->xs_smooth || a->Ps_smooth || a->x0_smooth ||
+                         a->P0_smooth || a->ok);
+  int rc = check_ekf_inputs("cpmpc_sim_rts", a, any, model, dtype, B, dyn_shared_host, dt, T);
+  if (rc) return rc;
+  if (!a->work) return fail(CPMPC_ERR_INVALID_ARG, "null argument (work)");
+  const int64_t need = cpmpc_sim_rts_work_rows(model, T);
+  if (a->work_rows < need)
+    return fail(CPMPC_ERR_INVALID_ARG, "work_rows is %lld, T = %d ticks need %lld (cpmpc_sim_rts_work_rows)",
+                (long long)a->work_rows, T, (long long)need);
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T, row = row_bytes(dtype, B);
+  // ok holds B int32: at most one row of either dtype
+  const ArraySpan outs[9] = {{a->x_final, nx, "x_final"},     {a->P_final, nx * nx, "P_final"},
+                             {a->xs, nt * nx, "xs"},          {a->nis, 1, "nis"},
+                             {a->xs_smooth, (nt + 1) * nx, "xs_smooth"}, {a->Ps_smooth, (nt + 1) * nx * nx, "Ps_smooth"},
+                             {a->x0_smooth, nx, "x0_smooth"}, {a->P0_smooth, nx * nx, "P0_smooth"},
+                             {a->ok, 1, "ok"}};
+  const ArraySpan ins[7] = {{a->x0, nx, "x0"},      {a->P0, nx * nx, "P0"}, {a->u, nt, "u"},          {a->fext, 4, "fext"},
+                            {a->dyn, np, "dyn"},    {a->y, nt * nx, "y"},   {a->tick_w, nt, "tick_w"}};
+  rc = check_no_overlap(outs, ins, row);
+  if (rc) return rc;
+  // the workspace is written by the first launch and read by the second while inputs are read and outputs written
+  const char* const w0 = (const char*)a->work;
+  const size_t w_bytes = (size_t)need * row;
+  auto over_work = [&](const ArraySpan& s) {
+    const char* const s0 = (const char*)s.p;
+    return s.p && s0 < w0 + w_bytes && w0 < s0 + s.rows * row;
+  };
+  for (const ArraySpan& s : ins)
+    if (over_work(s)) return fail(CPMPC_ERR_INVALID_ARG, "work overlaps %s (give the workspace an array of its own)", s.name);
+  for (const ArraySpan& s : outs)
+    if (over_work(s)) return fail(CPMPC_ERR_INVALID_ARG, "work overlaps %s (give the workspace an array of its own)", s.name);
+  return CPMPC_OK;
+}
+
+extern "C" int cpmpc_sim_rts_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                   const cpmpc_sim_rts* a, void* stream) {
+  int rc = check_sim_rts_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_rts(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
   });
 }
 

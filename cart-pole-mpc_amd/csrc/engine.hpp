@@ -255,6 +255,11 @@ struct Engine {
   // (sim_ekf_kernels.hpp)
   void (*sim_ekf)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_ekf* a,
                   hipStream_t stream);
+  // the Rauch-Tung-Striebel smoother over T ticks in two launches: the filter's recording form into a->work, then the
+  // backward pass over the record (sim_ekf_kernels.hpp: sim_ekf_record_kernel; sim_rts_kernels.hpp); the outputs of `a`
+  // that are not null
+  void (*sim_rts)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_rts* a,
+                  hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

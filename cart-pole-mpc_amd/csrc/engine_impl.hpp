@@ -20,6 +20,7 @@
 #include "sim_rollout_gn_kernels.hpp"
 #include "sim_rollout_gn_x0_kernels.hpp"
 #include "sim_ekf_kernels.hpp"
+#include "sim_rts_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -675,6 +676,23 @@ static void sim_ekf_impl(int64_t B, const double* dyn_shared_host, int n_sub, do
   });
 }
 
+// ---- the Rauch-Tung-Striebel smoother over T ticks, two launches (sim_ekf_record_kernel, sim_rts_kernel) ---------------
+template <typename R, typename M>
+static void sim_rts_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_rts* a,
+                         hipStream_t stream) {
+  const StateWeights<R, M::NX> sw = state_weights<R, M::NX>(a->w_host, 1.0), q = state_weights<R, M::NX>(a->q_host, 0.0);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    hipLaunchKernelGGL((sim_ekf_record_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                       plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->P0, (const R*)a->u, (const R*)a->y, sw, q,
+                       (const R*)a->tick_w, (R*)a->x_final, (R*)a->P_final, (R*)a->xs, (R*)a->nis, (R*)a->work);
+  });
+  if (a->xs_smooth || a->Ps_smooth || a->x0_smooth || a->P0_smooth || a->ok)
+    hipLaunchKernelGGL((sim_rts_kernel<R, M>), grid_for(B), dim3(64), 0, stream, B, T, (const R*)a->x0, (const R*)a->P0,
+                       (const R*)a->work, (R*)a->xs_smooth, (R*)a->Ps_smooth, (R*)a->x0_smooth, (R*)a->P0_smooth, a->ok);
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
 // linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
@@ -812,6 +830,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
                              &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
                              &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>, &sim_dyn_impl<R, M>,           \
                              &sim_param_jac_impl<R, M>,   &sim_rollout_impl<R, M>,     &sim_rollout_vjp_impl<R, M>,   \
-                             &sim_rollout_gn_impl<R, M>,  &sim_rollout_gn_x0_impl<R, M>, &sim_ekf_impl<R, M>};        \
+                             &sim_rollout_gn_impl<R, M>,  &sim_rollout_gn_x0_impl<R, M>, &sim_ekf_impl<R, M>,         \
+                             &sim_rts_impl<R, M>};                                                                   \
     return &e;                                                                                                       \
   }

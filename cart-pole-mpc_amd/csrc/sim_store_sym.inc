@@ -1,6 +1,6 @@
 // sim_store_sym.inc -- the NS x NS symmetric matrix whose lower triangle the lane keeps in its LDS fields, acc[tri(j, k)][lane],
 // to out [NS*NS][B] in full: (j, k) and (k, j) from the one kept value.  Included for H by sim_rollout_gn_kernel and
-// sim_rollout_gn_x0_kernel and for P_final by sim_ekf_kernel (as a function: more spill reloads in the tick loops, DESIGN.md 5l).
+// sim_rollout_gn_x0_kernel and for P_final by sim_ekf_body.inc (as a function: more spill reloads in the tick loops, DESIGN.md 5l).
 // Expects in scope: R, NS, out, B, p, acc and lane.
 #pragma unroll
     for (int j = 0; j < NS; ++j)

@@ -11,6 +11,15 @@ namespace cpmpc {
 __host__ __device__ constexpr int tri(int j, int k) { return j * (j + 1) / 2 + k; }
 __host__ __device__ constexpr int tri_sym(int a, int b) { return a >= b ? tri(a, b) : tri(b, a); }
 
+// What the Kalman filter's recording form stores per tick for the smoother's backward pass, as rows of B numbers from the
+// tick's base row t * ROWS: x- (NX), P- before the update (packed triangle, NH), A P (NX*NX, row j at AP + j*NX), the
+// filtered x (NX) and the filtered P (NH).  ROWS = 2 NX + 2 NH + NX^2: 44 for the 4-state model, 90 for the 6-state model.
+template <int NX>
+struct RtsRecord {
+  static constexpr int NH = tri(NX, 0);
+  static constexpr int XM = 0, PM = NX, AP = NX + NH, XF = NX + NH + NX * NX, PF = XF + NX, ROWS = PF + NH;
+};
+
 // the residual weights of the states, in the kernel's scalar type
 template <typename R, int NX>
 struct StateWeights {

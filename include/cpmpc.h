@@ -678,6 +678,61 @@ typedef struct cpmpc_sim_ekf {
 int cpmpc_sim_ekf_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                         const cpmpc_sim_ekf* a, void* stream);
 
+/* The RAUCH-TUNG-STRIEBEL SMOOTHER of B plants over T ticks: every state of the window given ALL of the window's measurements,
+ * with its covariance.  Forward it is the filter above, unchanged; state index 0 is x0 / P0 and index t is after tick t.  With
+ * x-_{t+1}, P-_{t+1} the prediction of tick t before its update and A_t its dx+/dx, backward from x^s_T = x_T, P^s_T = P_T
+ *     for t = T-1 .. 0:
+ *         G_t   = P_t A_t^T (P-_{t+1})^-1
+ *         d     = wrap(x^s_{t+1} - x-_{t+1})                    pole angles to the nearest turn
+ *         x^s_t = x_t + G_t d                                    then the pole angles are wrapped (where G_t d is not zero)
+ *         P^s_t = P_t + G_t (P^s_{t+1} - P-_{t+1}) G_t^T         exactly symmetric
+ * No inverse is formed: the rows of G_t come from the Cholesky factor of the diagonally scaled P-_{t+1}.  A tick whose P- is NOT
+ * POSITIVE DEFINITE (a diagonal entry not positive, or a pivot of the scaled matrix not above 8 NX eps or not finite) takes
+ * G_t = 0: index t's smoothed values are its filtered ones, the recursion goes on from them, and the problem's ok is 0.  That
+ * is the answer for P0 = 0 (the start is known).
+ * The inputs are cpmpc_sim_ekf's, with the same meaning, and a WORKSPACE `work` of work_rows rows of B numbers in `dtype`,
+ * work_rows >= cpmpc_sim_rts_work_rows(model, T) = T (2 NX + 2 NH + NX^2), NH = NX (NX + 1) / 2: 44 T rows for the 4-state
+ * model, 90 T for the 6-state model.  The forward pass stores there per tick x-, P-, A_t P_t and the filtered x and P; its
+ * contents after the call are not specified.
+ *     x_final, P_final, xs, nis: the filter's, bitwise cpmpc_sim_ekf_batch's on the same inputs;
+ *     xs_smooth [T+1][NX][B], Ps_smooth [T+1][NX*NX][B] (full and exactly symmetric): index T is x_final / P_final;
+ *     x0_smooth [NX][B], P0_smooth [NX*NX][B]: index 0 alone, for callers that want only the window's first state;
+ *     ok [B] int32: 1 where every tick's P- was positive definite.
+ * Every output is nullable, at least one must be given, and each is bitwise the same whichever others are asked for.  No
+ * output may overlap an input, and work may overlap nothing.  A problem with non-finite data has non-finite outputs and
+ * ok = 0; no other problem is affected.
+ * Device pointers in `dtype`; TWO launches on `stream` (one where only the filter's outputs are asked for), no host
+ * synchronisation, no allocation.  The rules of cpmpc_sim_ekf_batch, work == NULL, work_rows too small and the pointer rules
+ * above -> CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_rts {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_rts) */
+  const void* x0;         /* [NX][B], read only: the filtered state before the first tick */
+  const void* P0;         /* [NX*NX][B], read only: its covariance; the lower triangle is read */
+  const void* u;          /* [T][B] */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* y;          /* [T][NX][B] the measured x_{t+1}; required where some w_host[i] > 0 */
+  const void* tick_w;     /* [T][B] per-sample weights or NULL: ones (0 = that sample is missing) */
+  const double* w_host;   /* NX inverse variances of the measurement >= 0, or NULL: ones (0 = not measured) */
+  const double* q_host;   /* NX process-noise variances >= 0 added once a tick, or NULL: zeros */
+  void* work;             /* [work_rows][B] workspace, required */
+  int64_t work_rows;      /* >= cpmpc_sim_rts_work_rows(model, T) */
+  void* x_final;          /* [NX][B] or NULL */
+  void* P_final;          /* [NX*NX][B] or NULL */
+  void* xs;               /* [T][NX][B] or NULL */
+  void* nis;              /* [B] or NULL */
+  void* xs_smooth;        /* [T+1][NX][B] or NULL */
+  void* Ps_smooth;        /* [T+1][NX*NX][B] or NULL */
+  void* x0_smooth;        /* [NX][B] or NULL */
+  void* P0_smooth;        /* [NX*NX][B] or NULL */
+  int32_t* ok;            /* [B] or NULL */
+} cpmpc_sim_rts;
+/* rows of B numbers of cpmpc_sim_rts.work for T ticks of `model`; 0 for an unknown model or T < 1 */
+int64_t cpmpc_sim_rts_work_rows(int model, int T);
+int cpmpc_sim_rts_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                        const cpmpc_sim_rts* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
