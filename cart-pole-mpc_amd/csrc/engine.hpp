@@ -94,7 +94,7 @@ struct cpmpc_solver {
   int pipeline = CPMPC_PIPELINE_AUTO;
   bool refine_qp = false;  // CPMPC_CREATE_REFINE_QP: the double fused kernels refine the whole QP solution once
   bool beyond_parity = false;  // window_length * control_dt > cpmpc_max_parity_horizon(): cpmpc_horizon_beyond_parity()
-  int refine_passes = 0;   // split pipeline, double: passes of that refinement (1; 2 beyond the parity horizon: cpmpc_api.hip)
+  int refine_passes = 0;   // double, both pipelines: passes of that refinement (1; 2 beyond the parity horizon: cpmpc_api.hip; SolverArgs::refine_qp)
   bool wide_qp = false;    // CPMPC_CREATE_WIDE_QP (default for the 6-state model): the float fused kernels (compiled spacings) carry the QP's terminal part in double
   // staged fused pipeline (compaction of the still-active problems between stages); 0/0 = single launch
   // default 2 / 1 (round 4, tools/steady_state.py): in the warm-started closed loop most problems stop after one or two

@@ -35,6 +35,12 @@
   constexpr unsigned kTriv = trivial_cols<NX, M::NQ>(JaZeroCols<M>::value);
 #define SZ(r_, c_) (struct_zero<NX, M::NQ>(kTriv, (r_), (c_)))
   constexpr bool kTwoPass = NX > 4 && !kFullRefine;
+  // Round 7, the float 4-state kernels (two waves per SIMD): a control that a loop over the block's steps reads from LDS is
+  // read one step ahead, under the RK4 step before it, instead of being waited for a few instructions after the read is
+  // issued -- the linearisation's u and the line search's trial control (DESIGN.md section 5b).  Same values, same
+  // operations in the same order: results keep their bits (tests/test_gpu_fused_lds_order.py).  The double and 6-state
+  // kernels (one wave per SIMD, at their register limit) keep the order they had.
+  constexpr bool kUAhead = sizeof(R) == 4 && NX <= 4;
   CPMPC_TICK_INIT();
   CPMPC_CLOCK_BEGIN();
   const int lane = threadIdx.x;
@@ -120,9 +126,18 @@
       }
       typename M::StepCache chain;  // what the stages of a step share (models.hpp)
       {
+        // kUAhead: the control of step i + 1 is read under step i's RK4 (the last step reads its own again: no branch)
+        R u_lin = R(0);
+        if constexpr (kUAhead) u_lin = lds_u[0 * 64 + lane];
 #pragma unroll 1
         for (int i = 0; i < SP; ++i) {
-          const R u = lds_u[i * 64 + lane];
+          R u;
+          if constexpr (kUAhead) {
+            u = u_lin;
+            u_lin = lds_u[((i + 1 < SP) ? i + 1 : i) * 64 + lane];
+          } else {
+            u = lds_u[i * 64 + lane];
+          }
           R A[NX][NX], Bv[NX];
           rk4_step_jac_m<R, M, false>(k, a.dt, x, u, fe, A, Bv, chain);
           if constexpr (JaZeroCols<M>::value != 0u) {
@@ -1088,9 +1103,21 @@ CPMPC_SWEEP_PRAGMA
       }
       R u_before = (s == 0) ? u_prev : clampr(u_left + alpha * du_left, -a.u_lim, a.u_lim);
       typename M::StepCache chain;
+      // kUAhead: the trial control of step i + 1 is read and formed before step i's RK4, as prepare_kernel reads its
+      // u_next; the last step forms its own again instead of branching.  (Carrying the two loaded values themselves does
+      // not survive the optimiser: it folds a phi of loads back into one load at the top of the step.)
+      R u_nx = R(0);
+      if constexpr (kUAhead) u_nx = clampr(lds_u[0 * 64 + lane] + alpha * lds_du[0 * 64 + lane], -a.u_lim, a.u_lim);
 #pragma unroll 1
       for (int i = 0; i < SP; ++i) {
-        const R u = clampr(lds_u[i * 64 + lane] + alpha * lds_du[i * 64 + lane], -a.u_lim, a.u_lim);
+        R u;
+        if constexpr (kUAhead) {
+          u = u_nx;
+          const int in = (i + 1 < SP) ? i + 1 : i;
+          u_nx = clampr(lds_u[in * 64 + lane] + alpha * lds_du[in * 64 + lane], -a.u_lim, a.u_lim);
+        } else {
+          u = clampr(lds_u[i * 64 + lane] + alpha * lds_du[i * 64 + lane], -a.u_lim, a.u_lim);
+        }
         const R ru = a.wu * u, rd = a.wd * (u_before - u);
         fp += ru * ru + rd * rd;
         u_before = u;

@@ -1023,9 +1023,9 @@ __global__ __launch_bounds__(64) void qp_ls_kernel(const SolverArgs<R, M> a) {
     for (int i = 0; i < NX; ++i) q[i] = (Q)qw[i];
     // One step of iterative refinement of q with the residual taken through the factored operator
     // (S = W^T D^-1 W is a normal-equations matrix; see mpc_fused_body.inc).  fp64 only HERE: this kernel is bound by
-    // its workspace traffic and the pass re-reads W and T from HBM (+25 % bytes); the fused kernel, where the pass is
-    // on-chip, refines in fp32 too, so the two fp32 pipelines differ by that one correction (both are fp32-rounding
-    // level; the parity dtype is fp64, where both refine).
+    // its workspace traffic and the pass re-reads W and T from HBM (+25 % bytes).  The float fused kernels leave the
+    // pass out as well: they carry S in double (wide.hpp), so the rounding it repairs is not there (kRefinePasses in
+    // mpc_fused_body.inc).  The parity dtype is fp64, where both pipelines refine.
     if constexpr (sizeof(R) == 8) {
       R acc[NX];
 #pragma unroll
