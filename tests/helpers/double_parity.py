@@ -138,14 +138,15 @@ def _lane_over(over, terminal_weights, b):
     return dict(over, **dict(zip(NAMES, (float(w[0]), float(w[1]), float(w[nq]), float(w[nq + 1])))))
 
 
-def settled(orc, over, dyn, set_point, x0, opts=None, terminal_weights=None, rows=None):
+def settled(orc, over, dyn, set_point, x0, opts=None, terminal_weights=None, rows=None, model="double"):
     """The double oracle's cold step and where it can be trusted to 1e-7: -> ((u [N, B], pred [N, 6, B], status [B],
     iters [B]), settled mask [B], distance of the two oracles on u [B], the extended-precision u [N, B]).
     dyn [6] or [6, B], set_point a float or [B], terminal_weights None or [6, B] with both poles alike: with any of them per
     problem every lane is solved by an oracle built for that lane alone, from its own OptimizationParams.  rows: None or
     terminal weights [6, B] whose poles may differ, through the per-row override (oracle.step_batch_cold_rows; shared dyn and
-    set_point).  opts: oracle SolverOpts.  Cached per process on the values of all arguments; the arrays are read-only."""
-    key = _key(over, dyn, set_point, x0, opts, terminal_weights, rows)
+    set_point).  opts: oracle SolverOpts.  model: "double" (6 states) or "single" (4: tests/helpers/limits_parity.py).  Cached
+    per process on the values of all arguments; the arrays are read-only."""
+    key = _key(over, dyn, set_point, x0, opts, terminal_weights, rows, model)
     if key in _CACHE:
         return _CACHE[key]
     x0 = np.ascontiguousarray(x0, dtype=np.float64)
@@ -154,20 +155,20 @@ def settled(orc, over, dyn, set_point, x0, opts=None, terminal_weights=None, row
     if rows is not None:
         assert not per_problem
         p = orc.default_opt_params(**over)
-        u, pred, st, it, _ = orc.step_batch_cold_rows(p, dyn, set_point, x0, rows, opts=opts, want_pred=True, model="double")
-        u_ld, st_ld, it_ld, _, _ = orc.step_batch_cold_rows_ld(p, dyn, set_point, x0, rows, opts=opts, model="double")
+        u, pred, st, it, _ = orc.step_batch_cold_rows(p, dyn, set_point, x0, rows, opts=opts, want_pred=True, model=model)
+        u_ld, st_ld, it_ld, _, _ = orc.step_batch_cold_rows_ld(p, dyn, set_point, x0, rows, opts=opts, model=model)
     elif not per_problem:
         p = orc.default_opt_params(**over)
-        u, pred, st, it, _ = orc.step_batch_cold(p, dyn, set_point, x0, opts=opts, want_pred=True, model="double")
-        u_ld, st_ld, it_ld, _, _ = orc.step_batch_cold_ld(p, dyn, set_point, x0, opts=opts, model="double")
+        u, pred, st, it, _ = orc.step_batch_cold(p, dyn, set_point, x0, opts=opts, want_pred=True, model=model)
+        u_ld, st_ld, it_ld, _, _ = orc.step_batch_cold_ld(p, dyn, set_point, x0, opts=opts, model=model)
     else:
         lanes, lanes_ld = [], []
         for b in range(x0.shape[1]):
             p = orc.default_opt_params(**_lane_over(over, terminal_weights, b))
             d = dyn[:, b] if dyn.ndim == 2 else dyn
             s = float(set_point[b]) if np.ndim(set_point) == 1 else set_point
-            lanes.append(orc.step_batch_cold(p, d, s, x0[:, b:b + 1], opts=opts, want_pred=True, model="double")[:4])
-            lanes_ld.append(orc.step_batch_cold_ld(p, d, s, x0[:, b:b + 1], opts=opts, model="double")[:3])
+            lanes.append(orc.step_batch_cold(p, d, s, x0[:, b:b + 1], opts=opts, want_pred=True, model=model)[:4])
+            lanes_ld.append(orc.step_batch_cold_ld(p, d, s, x0[:, b:b + 1], opts=opts, model=model)[:3])
         u, pred, st, it = (np.concatenate([l[i] for l in lanes], axis=-1) for i in range(4))
         u_ld, st_ld, it_ld = (np.concatenate([l[i] for l in lanes_ld], axis=-1) for i in range(3))
     dist = np.abs(u - u_ld).max(axis=0)
@@ -230,6 +231,7 @@ def pole_rows():
 POLE_OVER = dict(OVER, max_iterations=3, **mix(ALL_COST))
 POLE_SEED = 63
 
+# (the retraction limits and the damping ladder: tests/helpers/limits_parity.py)
 OPTION_SETS = [dict(ls_alpha_growth=2.0, ls_alpha_growth_backtracked=1.0), dict(ls_alpha_growth=0.0),
                dict(ls_shrink_max=0.7, ls_shrink_min=0.2, armijo_c1=1e-2, max_line_search_iterations=3,
                     lambda_failure_init=1.0, penalty_rho=0.5)]          # tests/test_gpu_parity.py

@@ -282,6 +282,7 @@ def test_step_parity_configurations(pkg, orc, over):
 def test_step_parity_solver_options(pkg, orc, sopts, pipeline):
     """The knobs of this repo's SQP specification (cpmpc_solver_opts) mean the same in the
     kernels and in the oracle."""
+    # the retraction limits and the damping ladder are held by tests/test_gpu_limits_parity.py, not by these sets
     rng = np.random.default_rng(7)
     x0 = random_states(rng, 512)
     opt = pkg.BatchOptimization(pkg.default_params(**NO_TOL), max_batch=512, dtype=torch.float64, device=0,
