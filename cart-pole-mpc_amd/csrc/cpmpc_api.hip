@@ -124,8 +124,7 @@ extern "C" int cpmpc_model_num_params(int model) {
 // (run-time spacing, O(spacing^2) workspace traffic per interval); 0: not a spacing
 extern "C" int cpmpc_supported_state_spacing(int spacing) {
   if (spacing < 1) return 0;
-  return (spacing == 1 || spacing == 2 || spacing == 4 || spacing == 5 || spacing == 8 || spacing == 10 ||
-          spacing == 20) ? 2 : 1;
+  return linearize_specialised(spacing) ? 2 : 1;
 }
 
 static int validate_params(const cpmpc_params* p) {

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/cpmpc.h"
+#include "kernel_shapes.hpp"
 #include "workspace_layout.hpp"
 
 using namespace cpmpc;
@@ -125,33 +126,17 @@ CPMPC_HIDDEN int cpmpc_plan_stages(cpmpc_solver* s, int slot, int64_t B, bool ex
 // run fn(i) for i in [0, n) on the library's worker threads (the calling thread takes part); returns when all are done
 CPMPC_HIDDEN void host_parallel_for(int64_t n, void (*fn)(int64_t i, void* ctx), void* ctx);
 
-// fused pipeline: compiled specialisations for these (L = S-1, SP) pairs ...
-static inline bool fused_static(int L, int SP) {  // the default horizon's spacings (N = 40) and N = 20
-  return (L == 4 && SP == 10) || (L == 8 && SP == 5) || (L == 2 && SP == 10) || (L == 4 && SP == 5) ||
-         (L == 2 && SP == 20) || (L == 5 && SP == 8) || (L == 10 && SP == 4);
+// fused pipeline: compiled specialisations for some (L = S-1, SP) pairs, and a run-time-spacing variant (dynamic LDS) for
+// any other spacing with a compiled interval count whose per-wave LDS (80 scalars per lane and control for NX = 4) fits a
+// dynamic allocation (kernel_shapes.hpp: the lists and the layout)
+static inline bool fused_built(const cpmpc_solver* s) {
+  return fused_static(s->S - 1, s->SP) ||
+         (fused_dynamic_group(s->S - 1) && fused_dyn_lds_bytes(s->esize, s->NX, s->SP) <= kMaxDynamicLdsBytes);
 }
-// ... and a run-time-spacing variant (dynamic LDS) for any other spacing with one of these interval counts whose
-// per-wave LDS (80 scalars per lane and control for NX = 4) fits the 64 KB a dynamic allocation may take
-static inline size_t fused_dyn_bytes(const cpmpc_solver* s) {
-  const size_t col = (size_t)s->NX * s->esize;
-  const size_t g_bytes = col % 16 == 0 ? col : (col + 7) / 8 * 8;  // a column of Gamma in 16- or 8-byte pieces (mpc_fused.hpp)
-  return (size_t)s->SP * 64 * (4 * (size_t)s->esize + g_bytes);
-}
-static inline bool fused_dynamic(const cpmpc_solver* s) {
-  const int L = s->S - 1;
-  const bool l_ok = L == 2 || L == 4 || L == 5 || L == 8 || L == 10 || L == 16;
-  return l_ok && fused_dyn_bytes(s) <= 65536;
-}
-static inline bool fused_built(const cpmpc_solver* s) { return fused_static(s->S - 1, s->SP) || fused_dynamic(s); }
-
-// LDS a wave of the fused kernel takes for this handle (mpc_fused.hpp: u, du, (U^-1 g), 1/d per control and lane plus a
-// column of Gamma in 16-byte pieces; the slim layout of the double 6-state kernel keeps u, du and Gamma only)
+// LDS a wave of the fused kernel takes for this handle: the compiled pair's layout (slim or not), else the dynamic one
 static inline size_t fused_wave_lds_bytes(const cpmpc_solver* s) {
-  const size_t col = (size_t)s->NX * s->esize;
-  const size_t g_bytes = col % 16 == 0 ? col : (col + 7) / 8 * 8;
-  // (the slim layout is the double 6-state kernel's: mpc_fused.hpp, fused_slim)
-  const bool slim = s->esize == 8 && s->NX > 4 && !s->refine_qp && s->SP <= 10 && fused_static(s->S - 1, s->SP);
-  return (size_t)s->SP * 64 * ((slim ? 2 : 4) * (size_t)s->esize + g_bytes);
+  return fused_static(s->S - 1, s->SP) ? fused_static_lds_bytes(s->esize, s->NX, s->SP, s->refine_qp)
+                                       : fused_dyn_lds_bytes(s->esize, s->NX, s->SP);
 }
 
 static inline bool use_fused(const cpmpc_solver* s) {
@@ -164,7 +149,7 @@ static inline bool use_fused(const cpmpc_solver* s) {
   // CU: split).
   // (the other kernels keep what rounds 1-4 measured for them: fused wherever built)
   if (s->pipeline == CPMPC_PIPELINE_AUTO && s->model == CPMPC_MODEL_DOUBLE && s->dtype == CPMPC_F64 &&
-      3 * fused_wave_lds_bytes(s) > 160u * 1024u)
+      3 * fused_wave_lds_bytes(s) > kCuLdsBytes)
     return false;
   // AUTO beyond the parity horizon (fp64; round 6): the split pipeline, whose QP kernel runs TWO refinement passes there -- from
   // the second pass on the refined condensed solve is more accurate than a dense pivoted LU on the worst cold starts

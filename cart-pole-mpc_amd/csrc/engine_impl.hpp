@@ -11,6 +11,7 @@
 #include "mpc_kernels.hpp"
 #include "mpc_fused.hpp"
 #include "feedback_kernels.hpp"
+#include "plant_kernels.hpp"
 #include "plan_sensitivity_kernels.hpp"
 #include "plan_vjp_kernels.hpp"
 #include "plan_weight_vjp_kernels.hpp"
@@ -111,84 +112,44 @@ template <typename R, typename M>
 static void launch_linearize(const SolverArgs<R, M>& a, int SP, const XV<R, M::NX>* zx_in, const R* zu_in,
                              const int32_t* status, hipStream_t stream) {
   const dim3 grid = grid_for(a.B * (a.S - 1));
-#define CPMPC_LIN(SPV)                                                                                       \
-  case SPV:                                                                                                  \
-    hipLaunchKernelGGL((linearize_kernel<R, M, SPV>), grid, dim3(64), 0, stream, a, zx_in, zu_in, status);   \
-    break;
-  switch (SP) {
-    CPMPC_LIN(1)
-    CPMPC_LIN(2)
-    CPMPC_LIN(4)
-    CPMPC_LIN(5)
-    CPMPC_LIN(8)
-    CPMPC_LIN(10)
-    CPMPC_LIN(20)
-    default:  // no register-resident specialisation: run-time spacing, Gamma accumulated in the workspace
-      hipLaunchKernelGGL((linearize_dyn_kernel<R, M>), grid, dim3(64), 0, stream, a, zx_in, zu_in, status);
-      break;
-  }
-#undef CPMPC_LIN
+  const bool specialised = dispatch_value(SP, LinearizeSpacings{}, [&](auto sp) {
+    hipLaunchKernelGGL((linearize_kernel<R, M, decltype(sp)::value>), grid, dim3(64), 0, stream, a, zx_in, zu_in, status);
+  });
+  if (!specialised)  // no register-resident specialisation: run-time spacing, Gamma accumulated in the workspace
+    hipLaunchKernelGGL((linearize_dyn_kernel<R, M>), grid, dim3(64), 0, stream, a, zx_in, zu_in, status);
 }
 
-// The shared-parameters specialisation (model constants wave-uniform, in SGPRs) is used in fp32 only: the fp64
+// The instantiation of a fused kernel a launch takes, f(SHARED, REFINE) as std::bool_constants:
+// REFINE: the double kernels' refinement of the whole QP solution (CPMPC_CREATE_REFINE_QP), the float kernels' QP in double
+// (CPMPC_CREATE_WIDE_QP); constants through vector registers there (SHARED = false).
+// SHARED, the shared-parameters specialisation (model constants wave-uniform, in SGPRs), is used in fp32 only: the fp64
 // kernel already sits at the SGPR limit with its VGPR/AGPR file exhausted, and with the constants added to the
 // scalar pressure hipcc 7.2 produced wrong results for it (caught by the fp64 parity tests); there the constants
 // go through load_consts() into vector registers like per-problem parameters do.
+template <typename R, typename F>
+static auto with_fused_form(bool refine, bool shared_params, F f) {
+  if (refine) return f(std::false_type{}, std::true_type{});
+  if constexpr (sizeof(R) == 4) {
+    if (shared_params) return f(std::true_type{}, std::false_type{});
+  }
+  return f(std::false_type{}, std::false_type{});
+}
+
+// -> whether a kernel was launched: the compiled (L, SP) pair, else the run-time-spacing kernel of the group size L
 template <typename R, typename M>
-static void launch_fused(const SolverArgs<R, M>& a, int L, int SP, int max_iters, bool refine, hipStream_t stream) {
-  {
-    const int ppw = 64 / L;
-    const dim3 grid((unsigned)((a.B + ppw - 1) / ppw));
-    // REFINE = true: the double kernels' refinement of the whole QP solution (CPMPC_CREATE_REFINE_QP), the float kernels'
-    // QP in double (CPMPC_CREATE_WIDE_QP); constants through vector registers there (SHARED = false)
-#define CPMPC_FUSED(LV, SPV)                                                                                \
-  if (L == LV && SP == SPV) {                                                                               \
-    if (refine) {                                                                                           \
-      hipLaunchKernelGGL((fused_sqp_kernel<R, M, SPV, LV, false, true>), grid, dim3(64), 0, stream, a, max_iters); \
-      return;                                                                                               \
-    }                                                                                                       \
-    if constexpr (sizeof(R) == 4) {                                                                         \
-      if (a.dyn == nullptr) {                                                                               \
-        hipLaunchKernelGGL((fused_sqp_kernel<R, M, SPV, LV, true, false>), grid, dim3(64), 0, stream, a, max_iters); \
-        return;                                                                                             \
-      }                                                                                                     \
-    }                                                                                                       \
-    hipLaunchKernelGGL((fused_sqp_kernel<R, M, SPV, LV, false, false>), grid, dim3(64), 0, stream, a, max_iters);  \
-    return;                                                                                                 \
-  }
-    CPMPC_FUSED(4, 10)
-    CPMPC_FUSED(8, 5)
-    CPMPC_FUSED(2, 10)
-    CPMPC_FUSED(4, 5)
-    CPMPC_FUSED(2, 20)
-    CPMPC_FUSED(5, 8)
-    CPMPC_FUSED(10, 4)
-#undef CPMPC_FUSED
-    // no specialisation for this spacing: run-time SP, dynamic LDS
-    const size_t lds = fused_dyn_lds_bytes<R, M>(SP);
-#define CPMPC_FUSED_DYN(LV)                                                                                         \
-  if (L == LV) {                                                                                                    \
-    if (refine) {                                                                                                   \
-      hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, LV, false, true>), grid, dim3(64), lds, stream, a, max_iters); \
-      return;                                                                                                       \
-    }                                                                                                               \
-    if constexpr (sizeof(R) == 4) {                                                                                 \
-      if (a.dyn == nullptr) {                                                                                       \
-        hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, LV, true, false>), grid, dim3(64), lds, stream, a, max_iters); \
-        return;                                                                                                     \
-      }                                                                                                             \
-    }                                                                                                               \
-    hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, LV, false, false>), grid, dim3(64), lds, stream, a, max_iters);  \
-    return;                                                                                                         \
-  }
-    CPMPC_FUSED_DYN(2)
-    CPMPC_FUSED_DYN(4)
-    CPMPC_FUSED_DYN(5)
-    CPMPC_FUSED_DYN(8)
-    CPMPC_FUSED_DYN(10)
-    CPMPC_FUSED_DYN(16)
-#undef CPMPC_FUSED_DYN
-  }
+static bool launch_fused(const SolverArgs<R, M>& a, int L, int SP, int max_iters, bool refine, hipStream_t stream) {
+  const int ppw = 64 / L;
+  const dim3 grid((unsigned)((a.B + ppw - 1) / ppw));
+  return with_fused_form<R>(refine, a.dyn == nullptr, [&](auto shared, auto refined) {
+    constexpr bool SH = decltype(shared)::value, RF = decltype(refined)::value;
+    return dispatch_pair(L, SP, FusedStaticPairs{}, [&](auto pair) {
+      using P = decltype(pair);
+      hipLaunchKernelGGL((fused_sqp_kernel<R, M, P::SP, P::L, SH, RF>), grid, dim3(64), 0, stream, a, max_iters);
+    }) || dispatch_value(L, FusedDynamicGroups{}, [&](auto group) {  // no specialisation for this spacing: run-time SP
+      hipLaunchKernelGGL((fused_sqp_dyn_kernel<R, M, decltype(group)::value, SH, RF>), grid, dim3(64),
+                         fused_dyn_lds_bytes(sizeof(R), M::NX, SP), stream, a, max_iters);
+    });
+  });
 }
 
 template <typename R, typename M>
@@ -244,9 +205,15 @@ static int step_batch_impl(cpmpc_solver* s, int64_t B, const cpmpc_step_inputs* 
     a.active_count = nullptr;
     a.iter_cap = total;
     a.run_out_below = (int64_t)2048 * (64 / (s->S - 1));  // problems in one round of resident waves (2 per SIMD)
+    // (cannot be reached: launch_fused dispatches over the very lists fused_built() reads, kernel_shapes.hpp.  Should the
+    // two ever part, the step fails here instead of handing back the guess as a solution)
+    auto not_launched = [&] {
+      return fail(CPMPC_ERR_UNSUPPORTED, "no fused SQP kernel is compiled for L = S-1 = %d, SP = %d", s->S - 1, s->SP);
+    };
     span_begin(s, CPMPC_KERNEL_FUSED, stream, &sp);
-    launch_fused<R, M>(a, s->S - 1, s->SP, bounds[1], sizeof(R) == 8 ? s->refine_qp : wide_step, stream);
+    bool launched = launch_fused<R, M>(a, s->S - 1, s->SP, bounds[1], sizeof(R) == 8 ? s->refine_qp : wide_step, stream);
     span_end(s, stream, &sp);
+    if (!launched) return not_launched();
     for (int stage = 0; stage + 1 < n_stages; ++stage) {
       const int done = bounds[stage + 1];
       // three counters per host slot (chunks of a pipelined host step run concurrently), rotating: this compaction's, the
@@ -264,8 +231,9 @@ static int step_batch_impl(cpmpc_solver* s, int64_t B, const cpmpc_step_inputs* 
       a.active_list = s->active + col0;
       a.active_count = count;
       const int k = bounds[stage + 2] - done;
-      launch_fused<R, M>(a, s->S - 1, s->SP, k, sizeof(R) == 8 ? s->refine_qp : wide_step, stream);
+      launched = launch_fused<R, M>(a, s->S - 1, s->SP, k, sizeof(R) == 8 ? s->refine_qp : wide_step, stream);
       span_end(s, stream, &sp);
+      if (!launched) return not_launched();
     }
   } else {
     for (int it = 0; it < (int)s->params.max_iterations; ++it) {
@@ -475,19 +443,6 @@ static ExtForce<R> ext_from_host(const double* fext_host) {
   return fe;
 }
 
-template <typename R, typename M>
-static void linearize_batch_impl(cpmpc_solver* s, int64_t B, const double* dyn_shared_host, const void* z, void* c,
-                                 void* Phi, void* Gamma, hipStream_t st) {
-  SolverArgs<R, M> a;
-  fill_args<R, M>(s, B, a);
-  a.consts = M::template make<double>(dyn_shared_host);
-  hipLaunchKernelGGL((pack_z_kernel<R, M::NX>), grid_for(B), dim3(64), 0, st, B, s->cap, s->S, s->N, (const R*)z,
-                     a.dzx, a.dzu);
-  launch_linearize<R, M>(a, s->SP, a.dzx, a.dzu, nullptr, st);
-  hipLaunchKernelGGL((unpack_lin_kernel<R, M>), grid_for(B), dim3(64), 0, st, a, (R*)c, (R*)Phi, (R*)Gamma);
-}
-
-
 // ---- the remaining entry points of the table ----------------------------------------------------------------------
 template <typename R, typename M>
 static void pack_z_impl(cpmpc_solver* s, int64_t B, const void* z, hipStream_t stream) {
@@ -534,7 +489,7 @@ static void with_per_lane(bool per_lane, F f) {
   if (per_lane) f(std::true_type{});
   else f(std::false_type{});
 }
-// ... the kernels' first argument (mpc_kernels.hpp: PlantConsts): the per-problem array, or the shared set folded here
+// ... the kernels' first argument (plant_kernels.hpp: PlantConsts): the per-problem array, or the shared set folded here
 template <typename R, typename M, bool PER_LANE>
 static typename PlantConsts<R, M, PER_LANE>::Arg plant_consts_arg(const double* dyn_shared_host, const void* dyn) {
   if constexpr (PER_LANE) return (const R*)dyn;
@@ -694,9 +649,9 @@ static void sim_rts_impl(int64_t B, const double* dyn_shared_host, int n_sub, do
 }
 
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
-// All four calls start alike: the arguments of a linearisation at z, then launch_linearize exactly as
-// linearize_batch_impl does it (a caller's z goes through the step buffers dzx / dzu, which hold no state between calls;
-// z == NULL: the warm start itself, read only), then one lane per problem over Phi and Gamma.  Each call writes Phi,
+// All four calls start alike: the arguments of a linearisation at z, then launch_linearize (a caller's z goes through the
+// step buffers dzx / dzu, which hold no state between calls; z == NULL: the warm start itself, read only), then one lane
+// per problem over Phi and Gamma.  Each call writes Phi,
 // Gamma and cs, and the rows of Wk and Tk its kernel stores: scratch that every step recomputes before it reads it.
 template <typename R, typename M>
 static SolverArgs<R, M> gain_args(const cpmpc_solver* s, int64_t B, const cpmpc_gain_inputs* in) {
@@ -725,6 +680,17 @@ static PlanPoint<R, M> linearize_at(const cpmpc_solver* s, const SolverArgs<R, M
   }
   launch_linearize<R, M>(a, s->SP, at.zx, at.zu, nullptr, st);
   return at;
+}
+
+// the linearisation at a caller's z, unpacked from the workspace
+template <typename R, typename M>
+static void linearize_batch_impl(cpmpc_solver* s, int64_t B, const double* dyn_shared_host, const void* z, void* c,
+                                 void* Phi, void* Gamma, hipStream_t st) {
+  SolverArgs<R, M> a;
+  fill_args<R, M>(s, B, a);
+  a.consts = M::template make<double>(dyn_shared_host);
+  linearize_at<R, M>(s, a, z, st);
+  hipLaunchKernelGGL((unpack_lin_kernel<R, M>), grid_for(B), dim3(64), 0, st, a, (R*)c, (R*)Phi, (R*)Gamma);
 }
 
 // KERNEL<R, M, WIDEQ> of the enclosing template's R and M, one lane per problem: the wide form for a float handle s with
@@ -821,16 +787,27 @@ static int debug_read_impl(int which, unsigned long long* out) {
   return -1;
 }
 
-#define CPMPC_DEFINE_ENGINE(NAME, R, M)                                                                              \
-  const Engine* NAME() {                                                                                             \
-    static const Engine e = {&step_batch_impl<R, M>, &host_chunk_begin<R, M>, &host_chunk_end<R, M>, &pack_z_impl<R, M>, \
-                             &unpack_z_impl<R, M>,   &dynamics_impl<R, M>,   &rk4_impl<R, M>,      &sim_impl<R, M>,    \
-                             &sim_jac_impl<R, M>,                                                                    \
-                             &linearize_batch_impl<R, M>, &debug_read_impl, &feedback_gain_impl<R, M>,               \
-                             &feedback_apply_impl<R, M>,  &plan_sensitivity_impl<R, M>, &plan_update_impl<R, M>,      \
-                             &plan_vjp_impl<R, M>,        &plan_weight_vjp_impl<R, M>, &sim_dyn_impl<R, M>,           \
-                             &sim_param_jac_impl<R, M>,   &sim_rollout_impl<R, M>,     &sim_rollout_vjp_impl<R, M>,   \
-                             &sim_rollout_gn_impl<R, M>,  &sim_rollout_gn_x0_impl<R, M>, &sim_ekf_impl<R, M>,         \
-                             &sim_rts_impl<R, M>};                                                                   \
-    return &e;                                                                                                       \
+// The table of a (dtype, model) pair, its members filled by name: neighbours of one signature (the sim_* entries) cannot be
+// swapped unseen, and the order of engine.hpp's declarations is free.  A new member gets a line here.
+#define CPMPC_DEFINE_ENGINE(NAME, R, M)                                                                               \
+  const Engine* NAME() {                                                                                              \
+    static_assert(sizeof(Engine) == 25 * sizeof(void*), "an entry point of engine.hpp has no line below");            \
+    static const Engine e = [] {                                                                                      \
+      Engine t{};                                                                                                     \
+      t.step_batch = &step_batch_impl<R, M>;              t.host_chunk_begin = &host_chunk_begin<R, M>;               \
+      t.host_chunk_end = &host_chunk_end<R, M>;           t.pack_z = &pack_z_impl<R, M>;                              \
+      t.unpack_z = &unpack_z_impl<R, M>;                  t.dynamics = &dynamics_impl<R, M>;                          \
+      t.rk4 = &rk4_impl<R, M>;                            t.sim = &sim_impl<R, M>;                                    \
+      t.sim_jac = &sim_jac_impl<R, M>;                    t.linearize_batch = &linearize_batch_impl<R, M>;            \
+      t.debug_read = &debug_read_impl;                    t.feedback_gain = &feedback_gain_impl<R, M>;                \
+      t.feedback_apply = &feedback_apply_impl<R, M>;      t.plan_sensitivity = &plan_sensitivity_impl<R, M>;          \
+      t.plan_update = &plan_update_impl<R, M>;            t.plan_vjp = &plan_vjp_impl<R, M>;                          \
+      t.plan_weight_vjp = &plan_weight_vjp_impl<R, M>;    t.sim_dyn = &sim_dyn_impl<R, M>;                            \
+      t.sim_param_jac = &sim_param_jac_impl<R, M>;        t.sim_rollout = &sim_rollout_impl<R, M>;                    \
+      t.sim_rollout_vjp = &sim_rollout_vjp_impl<R, M>;    t.sim_rollout_gn = &sim_rollout_gn_impl<R, M>;              \
+      t.sim_rollout_gn_x0 = &sim_rollout_gn_x0_impl<R, M>; t.sim_ekf = &sim_ekf_impl<R, M>;                           \
+      t.sim_rts = &sim_rts_impl<R, M>;                                                                                \
+      return t;                                                                                                       \
+    }();                                                                                                              \
+    return &e;                                                                                                        \
   }

@@ -612,4 +612,28 @@ __device__ __forceinline__ void rk4_step_jac_m(const typename M::Consts& k, cons
   rk4_step_jac_m<R, M, HAS_EXT>(k, h, x, u, fe, A, Bv, sc);
 }
 
+// ---- scalar helpers of the SQP kernels and the plant kernels alike -------------------------------------------------------
+template <typename R>
+__device__ __forceinline__ R clampr(R v, R lo, R hi) {
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
+// running maximum for |dz|_inf of the full-step rule: one v_max.  The hardware maximum DROPS a NaN operand, so a step with
+// a NaN component may still be classed "tiny" here where the CPU restatement (which propagates the NaN) says "not tiny".
+// The two then differ only in the first trial step length (1 instead of alpha_start) of a line search that cannot
+// succeed either way: every trial point has a NaN component, its merit is non-finite, and both the Armijo test and the
+// full-step rule (which demands a finite merit) reject it -- same trial count, same rejection, same damping update.  In
+// the usual case the NaN has already made g.du or |J dz|^2 non-finite and the problem is QP_INDEFINITE before this.
+template <typename R>
+__device__ __forceinline__ R nan_max(R a, R b) {
+  return (sizeof(R) == 8) ? (R)__builtin_fmax((double)a, (double)b) : (R)__builtin_fmaxf((float)a, (float)b);
+}
+
+// wrap the pole angles of a state / state difference
+template <typename R, typename M>
+__device__ __forceinline__ void wrap_angles(R (&x)[M::NX]) {
+#pragma unroll
+  for (int t = 1; t < M::NQ; ++t) x[t] = mod_pi(x[t]);
+}
+
 }  // namespace cpmpc

@@ -26,6 +26,7 @@
 // Same algorithm as the split pipeline (same QP, same line search, same decisions); the sweeps associate
 // their sums differently, so results agree to rounding (fp64: 1e-9), not bitwise.
 #pragma once
+#include "kernel_shapes.hpp"
 #include "mpc_kernels.hpp"
 
 namespace cpmpc {
@@ -214,51 +215,16 @@ static __device__ unsigned long long g_fused_clock[4];  // sum of shader cycles,
 #define CPMPC_CLOCK_END() do { } while (0)
 #endif
 
-// Slim layout for the double kernel of the 6-state model (round 5): with (U^-1 g)_k in the slot of du_k (the previous step
-// is dead when sweep 1 writes it; sweep 1b turns it into v_k in place) and the 1/d_k of a lane's controls in registers, a
-// wave needs u + du + Gamma = (8 + 8 + 48) x SP x 64 bytes = 40 KB at SP = 10 instead of 60 KB: four waves per CU -- one per
-// SIMD, all the 512-register kernel can use -- instead of two.  Not for the REFINE instantiation
-// (its second solve needs gw and du side by side).  For a third wave per SIMD the fp32 4-state kernel with (U^-1 g)_k in the
-// slot of du_k measured 108.4 M re-plans/s against 116.3 M, and 99.0 M with the 1/d_k in registers too (round 3); the float
-// 6-state kernel in the slim layout at two waves per SIMD spilled 533 dwords, 33 against 51 M (round 5).
-template <typename R, typename M, int SP, bool REFINE>
-__host__ __device__ constexpr bool fused_slim() {
-  return sizeof(R) == 8 && M::NX > 4 && !REFINE && SP <= 10;
-}
-
-// ---- Gamma in LDS ---------------------------------------------------------------------------------------------------
-// A column of Gamma_s is an NX-vector: 16 bytes (float, NX = 4), 24 (float, NX = 6), 32 (double, NX = 4) or 48 (double,
-// NX = 6), stored as the pieces it fills at [(i * 64 + lane) * pieces + p].  Round 5 dropped the padding of the 6-state
-// columns to 32 / 64 bytes: Gamma is 30 KB instead of 40 KB per wave for the double 6-state kernel, three waves per CU
-// instead of two (and four with the slim layout above).  Lane-consecutive 16-byte planes, [(i * pieces + p) * 64 + lane],
-// remove the 2-way LDS bank conflicts of the wider columns (SQ_LDS_BANK_CONFLICT 7 800 -> 0 cycles per wave) but were
-// 0.5 % slower (round 4, fp64: 4.832 vs 4.805 ms; profiles/r04_f64_{planes,noplanes}_pmc_summary.json): the lone wave
-// never waited on the conflicts, and the second address per access cost more than they did.
-// A piece is 16 bytes where the column is a whole number of them (float / NX = 4: one; double / NX = 4: two; double /
-// NX = 6: three) and 8 bytes otherwise (float / NX = 6: 24 bytes = three pieces of 8 instead of the padded 32: 15 KB of Gamma
-// per wave instead of 20, which is what lets the float 6-state kernel's LDS fit eight waves per CU, round 5).
+// ---- LDS layout: kernel_shapes.hpp (the slim rule, Gamma's pieces, bytes per wave; why it is what it is) ----------------
 template <int BYTES>
 struct alignas(BYTES) GPieceT {
   unsigned w[BYTES / 4];
 };
 template <typename R, int NX>
-__host__ __device__ constexpr int fused_g_piece_bytes() {
-  return (NX * sizeof(R)) % 16 != 0 ? 8 : 16;
-}
-template <typename R, int NX>
-using GPieceOf = GPieceT<fused_g_piece_bytes<R, NX>()>;
-template <typename R, int NX>
-__host__ __device__ constexpr int fused_g_pieces() {
-  constexpr int PB = fused_g_piece_bytes<R, NX>();
-  return (int)((NX * sizeof(R) + PB - 1) / PB);
-}
-template <typename R, int NX>
-__host__ __device__ constexpr size_t fused_g_bytes() {  // LDS bytes of one column
-  return (size_t)fused_g_pieces<R, NX>() * fused_g_piece_bytes<R, NX>();
-}
+using GPieceOf = GPieceT<fused_g_piece_bytes(sizeof(R), NX)>;
 template <typename R, int NX>
 __device__ __forceinline__ XV<R, NX> fused_g_ld(const GPieceOf<R, NX>* g, int i, int lane) {
-  constexpr int K = fused_g_pieces<R, NX>();
+  constexpr int K = fused_g_pieces(sizeof(R), NX);
   XV<R, NX> v;
   GPieceOf<R, NX> pc[K];
 #pragma unroll
@@ -268,7 +234,7 @@ __device__ __forceinline__ XV<R, NX> fused_g_ld(const GPieceOf<R, NX>* g, int i,
 }
 template <typename R, int NX>
 __device__ __forceinline__ void fused_g_st(GPieceOf<R, NX>* g, int i, int lane, const XV<R, NX> v) {
-  constexpr int K = fused_g_pieces<R, NX>();
+  constexpr int K = fused_g_pieces(sizeof(R), NX);
   GPieceOf<R, NX> pc[K];
   __builtin_memcpy(pc, &v, sizeof pc <= sizeof v ? sizeof pc : sizeof v);
 #pragma unroll
@@ -282,12 +248,16 @@ template <typename R, typename M, int SP, int L, bool SHARED, bool REFINE>
 __global__ CPMPC_FUSED_BOUNDS void fused_sqp_kernel(const SolverArgs<R, M> a, const int max_iters) {
   constexpr int NX = M::NX;
   constexpr int PPW = 64 / L;  // problems per wave
-  constexpr bool kSlim = fused_slim<R, M, SP, REFINE>();
+  constexpr bool kSlim = fused_slim(sizeof(R), NX, SP, REFINE);
   __shared__ R lds_u[SP * 64];
   __shared__ R lds_du[SP * 64];
-  __shared__ GPieceOf<R, NX> lds_G[SP * 64 * fused_g_pieces<R, NX>()];  // column i of my Gamma_s (fused_g_ld / fused_g_st)
+  __shared__ GPieceOf<R, NX> lds_G[SP * 64 * fused_g_pieces(sizeof(R), NX)];  // column i of my Gamma_s (fused_g_ld / fused_g_st)
   __shared__ R lds_gw_own[kSlim ? 1 : SP * 64];  // (U^-1 g)_k of my controls
   __shared__ R lds_id[kSlim ? 1 : SP * 64];      // 1/d_k of my controls
+  // (the slim form's two one-element placeholders aside, exactly what the host is told a wave takes)
+  static_assert(sizeof lds_u + sizeof lds_du + sizeof lds_G + sizeof lds_gw_own + sizeof lds_id ==
+                    fused_static_lds_bytes(sizeof(R), NX, SP, REFINE) + (kSlim ? 2 * sizeof(R) : 0),
+                "the __shared__ arrays and kernel_shapes.hpp's layout disagree");
   R* const lds_gw = kSlim ? lds_du : lds_gw_own;
   R id_reg[kSlim ? SP : 1];
   constexpr int kSweepUnroll = kSlim ? SP : kFusedSweepUnroll;  // register-held 1/d_k need static indices: full unroll
@@ -315,10 +285,6 @@ __global__ CPMPC_FUSED_BOUNDS void fused_sqp_kernel(const SolverArgs<R, M> a, co
 
 // The same kernel for a state spacing without a compiled specialisation: SP is a.SP at run time, the LDS arrays are
 // carved from dynamic shared memory (fused_dyn_lds_bytes), the matrix powers use a run-time exponent.
-template <typename R, typename M>
-__host__ __device__ constexpr size_t fused_dyn_lds_bytes(int sp) {
-  return (size_t)sp * 64 * (4 * sizeof(R) + fused_g_bytes<R, M::NX>());
-}
 template <typename R, typename M, int L, bool SHARED, bool REFINE>
 __global__ CPMPC_FUSED_BOUNDS void fused_sqp_dyn_kernel(const SolverArgs<R, M> a, const int max_iters) {
   constexpr int NX = M::NX;
@@ -326,7 +292,7 @@ __global__ CPMPC_FUSED_BOUNDS void fused_sqp_dyn_kernel(const SolverArgs<R, M> a
   const int SP = a.SP;
   extern __shared__ __align__(32) unsigned char fused_dyn_lds[];
   GPieceOf<R, NX>* lds_G = reinterpret_cast<GPieceOf<R, NX>*>(fused_dyn_lds);   // widest elements first: stays aligned
-  R* lds_u = reinterpret_cast<R*>(lds_G + (size_t)SP * 64 * fused_g_pieces<R, NX>());
+  R* lds_u = reinterpret_cast<R*>(lds_G + (size_t)SP * 64 * fused_g_pieces(sizeof(R), NX));
   R* lds_du = lds_u + (size_t)SP * 64;
   R* lds_gw = lds_du + (size_t)SP * 64;
   R* lds_id = lds_gw + (size_t)SP * 64;

@@ -720,7 +720,7 @@ CPMPC_SWEEP_PRAGMA
     //           du_k = dut_k + et_k du_in;  ups_{k-1} = -wd2 / d_k uses my own pivots only
     R dxs[NX], dxe[NX];
     R gd_part = R(0), curv_part = R(0);
-    R dz_part = R(0);  // |dz|_inf over my piece of the step (nan_max drops a NaN component: see mpc_kernels.hpp)
+    R dz_part = R(0);  // |dz|_inf over my piece of the step (nan_max drops a NaN component: see models.hpp)
     R du_in = R(0);  // du of the control before my block (0 for interval 0: u_prev is fixed)
     {
       R Gt[NX], Ht[NX], dut = R(0), et = R(1);

@@ -141,29 +141,6 @@ __device__ __forceinline__ typename M::Consts load_consts(const SolverArgs<R, M>
   return M::template make<R>(prm);
 }
 
-template <typename R>
-__device__ __forceinline__ R clampr(R v, R lo, R hi) {
-  return v < lo ? lo : (v > hi ? hi : v);
-}
-
-// running maximum for |dz|_inf of the full-step rule: one v_max.  The hardware maximum DROPS a NaN operand, so a step with
-// a NaN component may still be classed "tiny" here where the CPU restatement (which propagates the NaN) says "not tiny".
-// The two then differ only in the first trial step length (1 instead of alpha_start) of a line search that cannot
-// succeed either way: every trial point has a NaN component, its merit is non-finite, and both the Armijo test and the
-// full-step rule (which demands a finite merit) reject it -- same trial count, same rejection, same damping update.  In
-// the usual case the NaN has already made g.du or |J dz|^2 non-finite and the problem is QP_INDEFINITE before this.
-template <typename R>
-__device__ __forceinline__ R nan_max(R a, R b) {
-  return (sizeof(R) == 8) ? (R)__builtin_fmax((double)a, (double)b) : (R)__builtin_fmaxf((float)a, (float)b);
-}
-
-// wrap the pole angles of a state / state difference
-template <typename R, typename M>
-__device__ __forceinline__ void wrap_angles(R (&x)[M::NX]) {
-#pragma unroll
-  for (int t = 1; t < M::NQ; ++t) x[t] = mod_pi(x[t]);
-}
-
 // ------------------------------------------------------------------------------------------------
 // prepare: initial guess.  One thread per problem.
 // ------------------------------------------------------------------------------------------------
@@ -271,168 +248,30 @@ __global__ __launch_bounds__(kPfBlock) void prepare_kernel(const SolverArgs<R, M
 // linearize: one thread per (problem, shooting interval).
 // Integrates x_s through SP controls with RK4, accumulating Phi = dx_end/dx_s and
 // Gamma = dx_end/du FORWARD (Phi <- A Phi, Gamma_j <- A Gamma_j, Gamma_i = B) so that nothing per
-// step has to be stored: the NX x SP block lives in registers with static indices.  Algebraically
-// equal to the reference's backward accumulation (optimization.cc:145-154).
+// step has to be stored.  Algebraically equal to the reference's backward accumulation
+// (optimization.cc:145-154).  One body for the two kernels (linearize_interval.inc); they differ in where
+// the Gamma columns of the interval live:
+//   linearize_kernel      the spacing at compile time: the NX x SP block in registers with static
+//                         indices, each control fetched one step ahead
+//   linearize_dyn_kernel  a.SP: the columns kept in the workspace (each thread re-reads and re-writes
+//                         only its own elements, coalesced over the wave).  O(SP^2) vector
+//                         read-modify-writes per interval: correct for any spacing, not fast for long ones.
 // ------------------------------------------------------------------------------------------------
 template <typename R, typename M, int SP>
 __global__ __launch_bounds__(64) void linearize_kernel(const SolverArgs<R, M> a, const XV<R, M::NX>* zx_in,
                                                         const R* zu_in, const int32_t* status) {
-  constexpr int NX = M::NX;
-  const int64_t gid = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  const int s = (int)(gid / a.B);
-  const unsigned p = (unsigned)(gid - (int64_t)s * a.B);
-  if (s >= a.S - 1) return;
-  const int64_t st = a.stride;
-  if (status != nullptr && status[IS_STATUS * st + p] != kTermNone) return;
-  const typename M::Consts k = load_consts(a, p);
-  const ExtForce<R> fe{R(0), R(0), R(0)};
-
-  R x[NX], xe[NX];
-  unpack<R, NX>(zx_in[(int64_t)s * st + p], x);
-  unpack<R, NX>(zx_in[(int64_t)(s + 1) * st + p], xe);
-  R Phi[NX][NX];
-  R Gam[SP][NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r)
-#pragma unroll
-    for (int c = 0; c < NX; ++c) Phi[r][c] = (r == c) ? R(1) : R(0);
-#pragma unroll
-  for (int j = 0; j < SP; ++j)
-#pragma unroll
-    for (int r = 0; r < NX; ++r) Gam[j][r] = R(0);
-
-  const R* zu = zu_in + (int64_t)(s * SP) * st;
-  R u_next = zu[p];
-  typename M::StepCache chain;  // the stages of a step share the sine / cosine base (models.hpp)
-#pragma unroll 1
-  for (int i = 0; i < SP; ++i) {
-    const R u = u_next;
-    if (i + 1 < SP) u_next = zu[(int64_t)(i + 1) * st + p];  // prefetch the next control
-    R A[NX][NX], Bv[NX];
-    rk4_step_jac_m<R, M, false>(k, a.dt, x, u, fe, A, Bv, chain);
-    // Phi <- A Phi
-    R T[NX][NX];
-#pragma unroll
-    for (int r = 0; r < NX; ++r)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R acc = A[r][0] * Phi[0][c];
-#pragma unroll
-        for (int m = 1; m < NX; ++m) acc += A[r][m] * Phi[m][c];
-        T[r][c] = acc;
-      }
-#pragma unroll
-    for (int r = 0; r < NX; ++r)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) Phi[r][c] = T[r][c];
-      // Gamma columns: j < i propagate, j == i is the new control's column.  `i` is uniform over
-      // the wave, so these are scalar branches and the register indices stay static.
-#pragma unroll
-    for (int j = 0; j < SP; ++j) {
-      if (j < i) {
-        R g[NX];
-#pragma unroll
-        for (int m = 0; m < NX; ++m) g[m] = Gam[j][m];
-#pragma unroll
-        for (int r = 0; r < NX; ++r) {
-          R acc = A[r][0] * g[0];
-#pragma unroll
-          for (int m = 1; m < NX; ++m) acc += A[r][m] * g[m];
-          Gam[j][r] = acc;
-        }
-      } else if (j == i) {
-#pragma unroll
-        for (int r = 0; r < NX; ++r) Gam[j][r] = Bv[r];
-      }
-    }
-  }
-  // wrap the angles once at the end of the interval, then the defect (optimization.cc:139,156-157)
-  wrap_angles<R, M>(x);
-  R c[NX];
-#pragma unroll
-  for (int t = 0; t < NX; ++t) c[t] = x[t] - xe[t];
-  wrap_angles<R, M>(c);
-  a.cs[(int64_t)s * st + p] = pack<R, NX>(c);
-#pragma unroll
-  for (int r = 0; r < NX; ++r) a.Phi[(int64_t)(NX * s + r) * st + p] = pack<R, NX>(Phi[r]);
-#pragma unroll
-  for (int j = 0; j < SP; ++j) a.Gam[(int64_t)(s * SP + j) * st + p] = pack<R, NX>(Gam[j]);
+  constexpr bool kInRegs = true;
+  constexpr int SPC = SP;
+#include "linearize_interval.inc"
 }
 
-// ------------------------------------------------------------------------------------------------
-// linearize for a state spacing without a register-resident specialisation: the same forward
-// accumulation with the spacing a run-time value and the Gamma columns of the interval kept in the
-// workspace (each thread re-reads and re-writes only its own elements, coalesced over the wave).
-// O(SP^2) vector read-modify-writes per interval: correct for any spacing, not fast for long ones.
-// ------------------------------------------------------------------------------------------------
 template <typename R, typename M>
 __global__ __launch_bounds__(64) void linearize_dyn_kernel(const SolverArgs<R, M> a, const XV<R, M::NX>* zx_in,
                                                            const R* zu_in, const int32_t* status) {
-  constexpr int NX = M::NX;
+  constexpr bool kInRegs = false;
+  constexpr int SPC = 1;
   const int SP = a.SP;
-  const int64_t gid = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  const int s = (int)(gid / a.B);
-  const unsigned p = (unsigned)(gid - (int64_t)s * a.B);
-  if (s >= a.S - 1) return;
-  const int64_t st = a.stride;
-  if (status != nullptr && status[IS_STATUS * st + p] != kTermNone) return;
-  const typename M::Consts k = load_consts(a, p);
-  const ExtForce<R> fe{R(0), R(0), R(0)};
-
-  R x[NX], xe[NX];
-  unpack<R, NX>(zx_in[(int64_t)s * st + p], x);
-  unpack<R, NX>(zx_in[(int64_t)(s + 1) * st + p], xe);
-  R Phi[NX][NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r)
-#pragma unroll
-    for (int c = 0; c < NX; ++c) Phi[r][c] = (r == c) ? R(1) : R(0);
-
-  const R* zu = zu_in + (int64_t)s * SP * st;
-  XV<R, NX>* gam = a.Gam + (int64_t)s * SP * st;
-  typename M::StepCache chain;
-#pragma unroll 1
-  for (int i = 0; i < SP; ++i) {
-    const R u = zu[(int64_t)i * st + p];
-    R A[NX][NX], Bv[NX];
-    rk4_step_jac_m<R, M, false>(k, a.dt, x, u, fe, A, Bv, chain);
-    R T[NX][NX];
-#pragma unroll
-    for (int r = 0; r < NX; ++r)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R acc = A[r][0] * Phi[0][c];
-#pragma unroll
-        for (int m = 1; m < NX; ++m) acc += A[r][m] * Phi[m][c];
-        T[r][c] = acc;
-      }
-#pragma unroll
-    for (int r = 0; r < NX; ++r)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) Phi[r][c] = T[r][c];
-#pragma unroll 1
-    for (int j = 0; j < i; ++j) {
-      R g[NX], gn[NX];
-      unpack<R, NX>(gam[(int64_t)j * st + p], g);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) {
-        R acc = A[r][0] * g[0];
-#pragma unroll
-        for (int m = 1; m < NX; ++m) acc += A[r][m] * g[m];
-        gn[r] = acc;
-      }
-      gam[(int64_t)j * st + p] = pack<R, NX>(gn);
-    }
-    gam[(int64_t)i * st + p] = pack<R, NX>(Bv);
-  }
-  wrap_angles<R, M>(x);
-  R c[NX];
-#pragma unroll
-  for (int t = 0; t < NX; ++t) c[t] = x[t] - xe[t];
-  wrap_angles<R, M>(c);
-  a.cs[(int64_t)s * st + p] = pack<R, NX>(c);
-#pragma unroll
-  for (int r = 0; r < NX; ++r) a.Phi[(int64_t)(NX * s + r) * st + p] = pack<R, NX>(Phi[r]);
+#include "linearize_interval.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1281,131 +1120,6 @@ __global__ __launch_bounds__(64) void unpack_lin_kernel(const SolverArgs<R, M> a
 #pragma unroll
     for (int t = 0; t < NX; ++t) Gam[(int64_t)(NX * i + t) * B + p] = v[t];
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// stand-alone pieces (parity tests, callers that want them); arrays packed [field][B]
-// ------------------------------------------------------------------------------------------------
-template <typename R, typename M>
-__global__ __launch_bounds__(64) void dynamics_kernel(int64_t B, typename M::Consts k, ExtForce<R> fe,
-                                                       const R* x, const R* u, R* f, R* Jx, R* Ju) {
-  constexpr int NX = M::NX, NQ = M::NQ;
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= B) return;
-  R xs[NX], acc[NQ], Ja[NQ][NX], Jua[NQ];
-#pragma unroll
-  for (int t = 0; t < NX; ++t) xs[t] = x[t * B + p];
-  M::template accel<true, true>(k, xs, u[p], fe, acc, Ja, Jua);
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-    f[i * B + p] = xs[NQ + i];
-    f[(NQ + i) * B + p] = acc[i];
-  }
-  if (Jx) {
-#pragma unroll
-    for (int i = 0; i < NQ; ++i)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        Jx[(i * NX + c) * B + p] = (c == NQ + i) ? R(1) : R(0);
-        Jx[((NQ + i) * NX + c) * B + p] = Ja[i][c];
-      }
-  }
-  if (Ju) {
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) {
-      Ju[i * B + p] = R(0);
-      Ju[(NQ + i) * B + p] = Jua[i];
-    }
-  }
-}
-
-template <typename R, typename M>
-__global__ __launch_bounds__(64) void rk4_kernel(int64_t B, typename M::Consts k, ExtForce<R> fe, R h,
-                                                  const R* x, const R* u, R* xn, R* A, R* Bm) {
-  constexpr int NX = M::NX;
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= B) return;
-  R xs[NX];
-#pragma unroll
-  for (int t = 0; t < NX; ++t) xs[t] = x[t * B + p];
-  if (A != nullptr || Bm != nullptr) {
-    R Am[NX][NX], Bv[NX];
-    rk4_step_jac_m<R, M, true>(k, h, xs, u[p], fe, Am, Bv);
-    if (A)
-#pragma unroll
-      for (int r = 0; r < NX; ++r)
-#pragma unroll
-        for (int c = 0; c < NX; ++c) A[(r * NX + c) * B + p] = Am[r][c];
-    if (Bm)
-#pragma unroll
-      for (int r = 0; r < NX; ++r) Bm[r * B + p] = Bv[r];
-  } else {
-    rk4_step_m<R, M, true>(k, h, xs, u[p], fe);
-  }
-#pragma unroll
-  for (int t = 0; t < NX; ++t) xn[t * B + p] = xs[t];
-}
-
-// The plant kernels' dynamics constants: the shared set's, folded on the host (a kernel argument, as it has always been), or
-// -- PER_LANE -- per-problem parameters dyn [NP][B], read by each lane and folded in the kernel as load_consts does.
-template <typename R, typename M, bool PER_LANE>
-struct PlantConsts {
-  using Arg = typename M::Consts;
-  __device__ __forceinline__ static const Arg& get(const Arg& k, int64_t, int64_t) { return k; }
-};
-template <typename R, typename M>
-struct PlantConsts<R, M, true> {
-  using Arg = const R*;
-  __device__ __forceinline__ static typename M::Consts get(const R* dyn, int64_t B, int64_t p) {
-    R prm[M::NP];
-#pragma unroll
-    for (int i = 0; i < M::NP; ++i) prm[i] = dyn[i * B + p];
-    return M::template make<R>(prm);
-  }
-};
-
-// The external forces of a lane: `fe` holds the shared set's and -- where fext [4][B] is given -- takes the lane's own (row 1
-// is not read).  In place: returned by value, the same loads come out as other instructions in some instantiations.
-template <typename R>
-__device__ __forceinline__ void load_ext_force(const R* fext, int64_t B, int64_t p, ExtForce<R>& fe) {
-  if (fext) {
-    fe.fbx = fext[p];
-    fe.fmx = fext[2 * B + p];
-    fe.fmy = fext[3 * B + p];
-  }
-}
-
-// Sub-step i of n_sub of one tick of the plant, Simulator::Step (simulator.cc:11-36): an RK4 step of 1 ms, the last one of
-// h_last, the control held, the angles wrapped.  The host evaluates the reference's `while (dt > 0) { SubStep(min(dt, 0.001));
-// dt -= 0.001; }` in double and passes the count and the last step, so f32 and f64 take the same sub-steps.  `chain` is the
-// tick's: a fresh StepCache before sub-step 0.
-template <typename R, typename M>
-__device__ __forceinline__ void plant_sub_step(const typename M::Consts& k, const ExtForce<R>& fe, int i, int n_sub, R h_last,
-                                               R uu, R (&xs)[M::NX], typename M::StepCache& chain) {
-  const R internal_dt = R(0.001);
-  const R h = (i + 1 == n_sub) ? h_last : internal_dt;
-  if (i % 8 == 0) chain.invalidate();  // (dead store: see TrigBase::valid)
-  rk4_step_m<R, M, true>(k, h, xs, uu, fe, chain);
-  wrap_angles<R, M>(xs);
-}
-
-template <typename R, typename M, bool PER_LANE = false>
-__global__ __launch_bounds__(64) void sim_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg, ExtForce<R> fe_shared,
-                                                  const R* fext, int n_sub, R h_last, const R* u, R* state) {
-  constexpr int NX = M::NX;
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= B) return;
-  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
-  ExtForce<R> fe = fe_shared;
-  load_ext_force<R>(fext, B, p, fe);
-  R xs[NX];
-#pragma unroll
-  for (int t = 0; t < NX; ++t) xs[t] = state[t * B + p];
-  const R uu = u[p];
-  typename M::StepCache chain;
-  for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
-#pragma unroll
-  for (int t = 0; t < NX; ++t) state[t * B + p] = xs[t];
 }
 
 }  // namespace cpmpc

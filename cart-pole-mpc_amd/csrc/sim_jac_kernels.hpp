@@ -16,7 +16,7 @@
 
 namespace cpmpc {
 
-// PER_LANE: per-problem dynamics parameters (mpc_kernels.hpp: PlantConsts); the default is the shared set.
+// PER_LANE: per-problem dynamics parameters (plant_kernels.hpp: PlantConsts); the default is the shared set.
 template <typename R, typename M, bool PER_LANE = false>
 __global__ __launch_bounds__(64) void sim_jac_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg,
                                                       ExtForce<R> fe_shared, const R* fext,

@@ -4,7 +4,7 @@
 // h_last, the control held over the tick, the pole angles wrapped after each sub-step.  dt, the external forces and the
 // dynamics parameters are those of every tick.  One problem per lane, no LDS; the tick loop stays on the device.
 //
-// sim_rollout_kernel: a tick is n_sub calls of plant_sub_step (mpc_kernels.hpp), the function sim_kernel's loop calls; after
+// sim_rollout_kernel: a tick is n_sub calls of plant_sub_step (plant_kernels.hpp), the function sim_kernel's loop calls; after
 // tick t it stores x_{t+1} to xs [T][NX][B] (field t*NX + r) and after the last one to x_final [NX][B], each where its pointer
 // is given (a wave-uniform choice).
 //

@@ -3,7 +3,7 @@
 // in scope, because as functions they moved registers, spills and occupancy of kernels at the register limit:
 // sim_phi_step.inc (Phi <- A Phi), sim_window_residual.inc, sim_normal_eq.inc (g, H of a tick), sim_store_sym.inc.
 #pragma once
-#include "mpc_kernels.hpp"
+#include "plant_kernels.hpp"
 
 namespace cpmpc {
 

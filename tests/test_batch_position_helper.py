@@ -89,19 +89,22 @@ def test_first_difference_finds_a_planted_bit(dtype, bit):
 
 
 def test_the_gpu_case_list_names_every_fused_specialisation():
-    """Every (L, SP) pair and every run-time-spacing interval count that launch_fused (csrc/engine_impl.hpp) can reach is a
-    4-state shape of tests/test_gpu_position_independence.py: a specialisation added there without a case here fails this."""
+    """Every (L, SP) pair and every run-time-spacing interval count that launch_fused (csrc/engine_impl.hpp) can reach -- the
+    two lists of csrc/kernel_shapes.hpp it dispatches over -- is a 4-state shape of tests/test_gpu_position_independence.py:
+    a specialisation added there without a case here fails this."""
     import os
     import re
 
     import test_gpu_position_independence as cases
     from conftest import ROOT
 
-    with open(os.path.join(ROOT, "cart-pole-mpc_amd", "csrc", "engine_impl.hpp")) as fh:
+    with open(os.path.join(ROOT, "cart-pole-mpc_amd", "csrc", "kernel_shapes.hpp")) as fh:
         src = fh.read()
-    compiled = {(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"^\s*CPMPC_FUSED\((\d+), (\d+)\)", src, re.M)}
-    dynamic = {int(m.group(1)) for m in re.finditer(r"^\s*CPMPC_FUSED_DYN\((\d+)\)", src, re.M)}
-    assert len(compiled) >= 7 and len(dynamic) >= 6, (compiled, dynamic)   # the patterns still find the two macro lists
+    pairs = re.search(r"using FusedStaticPairs = FusedPairList<(.*?)>;", src, re.S).group(1)
+    compiled = {(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"FusedPair<(\d+), (\d+)>", pairs)}
+    groups = re.search(r"using FusedDynamicGroups = std::integer_sequence<int,([\d, ]*)>;", src).group(1)
+    dynamic = {int(v) for v in groups.split(",")}
+    assert len(compiled) >= 7 and len(dynamic) >= 6, (compiled, dynamic)   # the patterns still find the two lists
     shapes = {(N // sp, sp) for N, sp in cases.FUSED_SHAPES["single"]}
     assert all(N % sp == 0 for N, sp in cases.FUSED_SHAPES["single"] + cases.FUSED_SHAPES["double"])
     assert compiled <= shapes, compiled - shapes

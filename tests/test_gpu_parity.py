@@ -886,3 +886,91 @@ def test_pipeline_selection(pkg):
     assert opt6.pipeline() == "split"
     opt6.set_pipeline("fused")
     assert opt6.pipeline() == "fused"
+
+
+# ---- every compiled form of the fused kernel is reached, and what is not built is refused ------------------------------
+# (window_length, state_spacing): the seven compiled (S-1, state_spacing) pairs, then one run-time-spacing shape per
+# compiled group size S-1 = 2, 4, 5, 8, 10, 16, then shapes with neither
+FUSED_STATIC_SHAPES = [(40, 10), (40, 5), (20, 10), (20, 5), (40, 20), (40, 8), (40, 4)]
+FUSED_DYNAMIC_SHAPES = [(6, 3), (12, 3), (15, 3), (24, 3), (30, 3), (48, 3)]
+FUSED_NOT_BUILT_SHAPES = [(21, 7), (40, 40), (40, 2)]
+DYN_DOUBLE = [1.0, 0.1, 0.1, 0.25, 0.2, 9.81]
+# the five instantiation forms of a fused kernel: creation options, and whether the parameters go per problem
+FUSED_FORMS = {
+    "f32_shared": (dict(dtype=torch.float32, wide_qp=False), False),
+    "f32_per_problem": (dict(dtype=torch.float32, wide_qp=False), True),
+    "f32_wide": (dict(dtype=torch.float32, wide_qp=True), False),
+    "f64": (dict(dtype=torch.float64, refine_qp=False), False),
+    "f64_refine": (dict(dtype=torch.float64, refine_qp=True), False),
+}
+FUSED_B = 70  # ragged for every group size: 70 is no multiple of 64 // L for L in {2, 4, 5, 8, 10, 16}
+
+
+def _fused_form_case(pkg, model, form, N, sp):
+    """-> (handle, x0, dyn) of one case: a cold start of FUSED_B problems from random_states (the 6-state model takes the
+    second pole's angle and rate from a second draw), two iterations, no exits."""
+    kw, per_problem = FUSED_FORMS[form]
+    dtype = kw["dtype"]
+    rng = np.random.default_rng(1000 * N + sp)
+    x0 = random_states(rng, FUSED_B)
+    dyn = DYN_UI
+    if model == "double":
+        x2 = random_states(rng, FUSED_B)
+        x0 = np.stack([x0[0], x0[1], x2[1], x0[2], x0[3], x2[3]])
+        dyn = DYN_DOUBLE
+    if per_problem:
+        dyn = T(np.tile(np.asarray(dyn)[:, None], (1, FUSED_B)), dtype)
+    over = dict(NO_TOL, window_length=N, state_spacing=sp, max_iterations=2)
+    opt = pkg.BatchOptimization(pkg.default_params(**over), max_batch=FUSED_B, device=0, model=model, **kw)
+    return opt, T(x0, dtype), dyn
+
+
+@pytest.mark.parametrize("N,sp", FUSED_STATIC_SHAPES + FUSED_DYNAMIC_SHAPES)
+@pytest.mark.parametrize("form", list(FUSED_FORMS))
+@pytest.mark.parametrize("model", ["single", "double"])
+def test_every_compiled_fused_form_is_reached(pkg, model, form, N, sp):
+    """Every (S-1, state_spacing) shape the fused pipeline accepts, in each of the five forms its kernels are instantiated in
+    and for both models, runs an SQP kernel.  Iterations are counted by the SQP kernel alone: prepare_kernel stores
+    iterations = 0 for every problem and finalize_kernel only copies the workspace's count to the output, so a step whose
+    SQP launch is missing ends with iterations == 0 on every lane and cannot pass.  The double forms are also held to the
+    split pipeline on the same handle (the bound of test_fused_with_groups_that_straddle_dpp_rows)."""
+    opt, x0, dyn = _fused_form_case(pkg, model, form, N, sp)
+    opt.set_pipeline("fused")
+    assert opt.pipeline() == "fused"
+    out = opt.step(x0, dyn, 0.0, want_stats=True)
+    its, u, st = N_(out.iterations), N_(out.u), N_(out.status)
+    print("iterations min %d max %d, finite u %d / %d, status %s" % (its.min(), its.max(), np.isfinite(u).all(axis=0).sum(),
+                                                                      FUSED_B, sorted(set(st.tolist()))))
+    assert (its == 2).all() and np.isfinite(u).all()
+    if x0.dtype == torch.float64:
+        opt.set_pipeline("split")
+        opt.reset()
+        out2 = opt.step(x0, dyn, 0.0, want_stats=True, out=pkg.BatchOutputs())
+        d = np.abs(N_(out2.u) - u).max()
+        print("fused vs split: max |du| %.3e, status equal %s" % (d, bool((N_(out2.status) == st).all())))
+        assert (N_(out2.status) == st).all() and d < 1e-6
+
+
+@pytest.mark.parametrize("N,sp", FUSED_NOT_BUILT_SHAPES)
+@pytest.mark.parametrize("form", list(FUSED_FORMS))
+@pytest.mark.parametrize("model", ["single", "double"])
+def test_fused_pipeline_refuses_a_shape_that_is_not_built(pkg, model, form, N, sp):
+    opt, _, _ = _fused_form_case(pkg, model, form, N, sp)
+    assert opt.pipeline() == "split"
+    with pytest.raises(pkg.CpmpcError) as ei:
+        opt.set_pipeline("fused")
+    assert ei.value.code == pkg.capi.ERR_UNSUPPORTED
+
+
+def test_fused_pipeline_refuses_more_dynamic_lds_than_a_launch_may_take(pkg):
+    """(window_length, state_spacing) = (26, 13), two intervals: a wave of the double 6-state run-time-spacing kernel would
+    take 13 * 64 * (4 * 8 + 48) = 66 560 bytes, more than the 65 536 a dynamic allocation may; the float 4-state kernel's
+    13 * 64 * (4 * 4 + 16) = 26 624 fit."""
+    opt, _, _ = _fused_form_case(pkg, "double", "f64", 26, 13)
+    with pytest.raises(pkg.CpmpcError) as ei:
+        opt.set_pipeline("fused")
+    assert ei.value.code == pkg.capi.ERR_UNSUPPORTED
+    opt, x0, dyn = _fused_form_case(pkg, "single", "f32_shared", 26, 13)
+    opt.set_pipeline("fused")
+    out = opt.step(x0, dyn, 0.0, want_stats=True)
+    assert (N_(out.iterations) == 2).all() and np.isfinite(N_(out.u)).all()
