@@ -711,10 +711,11 @@ def plan_update(u_nom, K=None, x_nom=None, x=None, k_sp=None, sp_nom=None, sp=No
     return out
 
 
-def _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a=None, ticks=False):
+def _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a=None, ticks=False, u_field="u"):
     """What every plant call reads, checked: state [nx, B]; u [B], or with `ticks` [T, B], T >= 1; fext None or [4, B];
     params np floats or an [np, B] tensor (None: the caller marshals them itself), for dims = _model_dims(model).  Where a
-    struct `a` is given they are set on it: the step structs call the state `state`, the rollout structs `x0`.
+    struct `a` is given they are set on it: the step structs call the state `state`, the rollout structs `x0`; the controls
+    go to `u_field` (cpmpc_sim_rollout_fb calls them u_nom).
     -> (B, T, host params or None, device pointer of the params or None, the shared forces as the host array that the call
     reads before it returns: the caller holds it, and the host params, until then)."""
     _, nx, npar = dims
@@ -725,9 +726,9 @@ def _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a=None, ticks=Fa
         raise ValueError("state must be [%d, B]" % nx)
     B, T = shape[1], 1
     if ticks:
-        _require_cuda_tensor(u, "u", dtp)
+        _require_cuda_tensor(u, u_field, dtp)
         if u.dim() != 2 or u.shape[0] < 1 or u.shape[1] != B:
-            raise ValueError("u must be [T, B] with T >= 1")
+            raise ValueError("%s must be [T, B] with T >= 1" % u_field)
         T = u.shape[0]
     else:
         _require_cuda_tensor(u, "u", dtp, (B,))
@@ -742,7 +743,7 @@ def _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a=None, ticks=Fa
     shared = capi.dbl_array([f_base[0], f_base[1], f_mass[0], f_mass[1]], 4)
     if a is not None:
         setattr(a, "x0" if ticks else "state", state.data_ptr())
-        a.u = u.data_ptr()
+        setattr(a, u_field, u.data_ptr())
         a.fext_host = C.cast(shared, C.POINTER(C.c_double))
         if fext is not None:
             a.fext = fext.data_ptr()
@@ -1371,6 +1372,93 @@ def sim_rts(params, dt, state, cov, u, y, weights, process_noise=None, tick_weig
     return {name: res[name] for name in want}
 
 
+def sim_lqr(params, dt, state, u, xs, q, r, terminal=None, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+            want=("K", "P0")):
+    """The time-varying LQR gains along a plant trajectory in ONE launch (include/cpmpc.h: cpmpc_sim_lqr_batch): the backward
+    Riccati recursion of the cost sum_t (d_t^T diag(q) d_t + r du_t^2) + d_T^T P_T d_T along the trajectory state [nx, B],
+    u [T, B], xs [T, nx, B] -- a sim_rollout_states call's at the same inputs (its last row is not read; None is allowed for
+    T = 1).  Per tick, last to first, with Phi and gamma the tick's sim_step_jacobian A and Bu at (x_t, u[t]):
+        v = P gamma,  s = r + gamma . v,  k_t = -(Phi^T v) / s,  Acl = Phi + gamma k_t^T,
+        P = diag(q) + r k_t k_t^T + Acl^T P Acl.
+    The plant has one input: no matrix is inverted.  q: nx weights >= 0 (None: ones); r: the control weight, > 0.
+    terminal: a tensor [nx, nx, B] for P_T (its lower triangle terminal[j, k], k <= j, is what is read: a call's "P0" chains
+    windows), a list of nx weights >= 0 for a diagonal P_T, or None: diag(q).
+
+    Returns a dict with the entries named in `want`,
+        "K"  [T, nx, B]   K[t] = k_t, applied as u = u_nom[t] + K[t] . (x_t - x_nom_t): what sim_rollout_feedback takes,
+        "P0" [nx, nx, B]  the cost-to-go at the window's start, exactly symmetric.
+    The gains belong to the PLANT's map at dt (1 ms sub-steps, the control held over the tick), not to a controller's model of
+    it; the clamp of the control and feedback inside a tick are not modelled.  dt = 0: K = 0, P0 = P_T + T diag(q).
+    params (np numbers or an [np, B] tensor), dt and the forces as sim_rollout_states'."""
+    want = _want_tuple(want, ("K", "P0"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimLqr(struct_size=C.sizeof(capi.SimLqr), r=float(r))
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    if xs is not None:
+        _require_cuda_tensor(xs, "xs", dtp, (T, nx, B))
+        a.xs = xs.data_ptr()
+    elif T > 1:
+        raise ValueError("xs (a sim_rollout_states call's) is required when T > 1")
+    if q is not None:
+        q_host = capi.dbl_array(q, nx)   # read by the call itself, before it returns
+        a.q_host = C.cast(q_host, C.POINTER(C.c_double))
+    if isinstance(terminal, torch.Tensor):
+        _require_cuda_tensor(terminal, "terminal", dtp, (nx, nx, B))
+        a.PT = terminal.data_ptr()
+    elif terminal is not None:
+        qf_host = capi.dbl_array(terminal, nx)
+        a.qf_host = C.cast(qf_host, C.POINTER(C.c_double))
+    res = _alloc_outputs(a, want, {"K": ("K", (T, nx, B)), "P0": ("P0", (nx, nx, B))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_lqr_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a), _stream_ptr()))
+    return res
+
+
+def sim_rollout_feedback(params, dt, state, u_nom, K, x0_nom, xs_nom, u_limit=float("inf"), fext=None, f_base=(0.0, 0.0),
+                         f_mass=(0.0, 0.0), model="single", want=("xs", "us")):
+    """T plant ticks under an affine feedback law in ONE launch (include/cpmpc.h: cpmpc_sim_rollout_fb_batch): from
+    state [nx, B] (read, not changed), per tick
+        d = wrap(x_t - x_nom_t),  u_t = clamp(u_nom[t] + K[t] . d, +-u_limit),  x_{t+1} = the plant's tick from x_t under u_t,
+    with x_nom_0 = x0_nom [nx, B], x_nom_t = xs_nom[t - 1] (xs_nom [T, nx, B]: a sim_rollout_states call's; its last row is not
+    read; None is allowed for T = 1) and the pole-angle differences wrapped to the nearest turn.  u_nom [T, B]; K [T, nx, B]
+    is sim_lqr's "K", or None: no feedback (x0_nom and xs_nom are then not read).  u_limit > 0, infinity: no clamp.  The
+    control is formed at the tick's start and held over it: there is no feedback inside a tick, and sim_lqr does not know of
+    the clamp.  params and the forces are THIS call's own plant and may differ from those the nominal trajectory and the gains
+    were made with: model mismatch is the point.
+
+    Returns a dict with the entries named in `want`,
+        "xs"      [T, nx, B]  the state after every tick,
+        "x_final" [nx, B]     the state after the last tick,
+        "us"      [T, B]      the controls applied.
+    With K None and u_limit infinite, xs is sim_rollout_states' bit for bit; with state == x0_nom and the nominal trajectory's
+    own parameters the call reproduces the nominal rollout bit for bit."""
+    want = _want_tuple(want, ("xs", "x_final", "us"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimRolloutFb(struct_size=C.sizeof(capi.SimRolloutFb), u_limit=float(u_limit))
+    B, T, host, _, _held = _plant_inputs(dims, state, u_nom, params, fext, f_base, f_mass, a, ticks=True, u_field="u_nom")
+    if K is not None:
+        _require_cuda_tensor(K, "K", dtp, (T, nx, B))
+        a.K = K.data_ptr()
+        if x0_nom is None:
+            raise ValueError("x0_nom (the nominal start) is required where K is given")
+        if xs_nom is None and T > 1:
+            raise ValueError("xs_nom (a sim_rollout_states call's) is required where K is given and T > 1")
+    if x0_nom is not None:
+        _require_cuda_tensor(x0_nom, "x0_nom", dtp, (nx, B))
+        a.x0_nom = x0_nom.data_ptr()
+    if xs_nom is not None:
+        _require_cuda_tensor(xs_nom, "xs_nom", dtp, (T, nx, B))
+        a.xs_nom = xs_nom.data_ptr()
+    res = _alloc_outputs(a, want, {"xs": ("xs", (T, nx, B)), "x_final": ("x_final", (nx, B)), "us": ("us", (T, B))}, dtp,
+                         state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_rollout_fb_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                          _stream_ptr()))
+    return res
+
+
 def _full_covariance(cov, nx, batch, dtype, name):
     """cov [nx, B] (a diagonal) or [nx, nx, B] -> a fresh [nx, nx, B] tensor"""
     _require_cuda_tensor(cov, name, dtype)
@@ -1599,6 +1687,17 @@ class BatchSimulator:
         self.state = res["x_final"]
         return res["xs"]
 
+    def rollout_feedback(self, params, dt, u_nom, K, x0_nom, xs_nom, u_limit=float("inf"), f_base=(0.0, 0.0), f_mass=(0.0, 0.0),
+                         fext=None):
+        """T step() calls under u_nom[t] + K[t] . wrap(x_t - x_nom_t), clamped to +-u_limit, in one launch
+        (sim_rollout_feedback): the state becomes the one after the last tick; returns (xs [T, nx, B], us [T, B]), the state
+        after every tick and the controls applied."""
+        res = sim_rollout_feedback(params.detach() if isinstance(params, torch.Tensor) else params, dt, self.state, u_nom, K,
+                                   x0_nom, xs_nom, u_limit=u_limit, fext=fext, f_base=f_base, f_mass=f_mass, model=self.model,
+                                   want=("xs", "x_final", "us"))
+        self.state = res["x_final"]
+        return res["xs"], res["us"]
+
     def rollout_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """rollout() with a backward: xs = sim_rollout(params, dt, self.state, u, ...) is returned, attached to the autograd
         graph of the state before the rollout, of u and -- where it is an [np, B] tensor requiring grad -- of params;
@@ -1723,6 +1822,63 @@ class ClosedLoop:
                 r = o.step(s.get_state(), dyn_i, sp, want_predicted=False, want_stats=want_stats, out=out)
                 s.step(pd, dt, r.u[0].contiguous())
         self.ticks += 1
+
+    def tick_hold(self, dyn, m, q, r, set_point=0.0, dt=0.01, want_stats=True, fext=None, plant_dyn=None, terminal=None):
+        """One re-plan, then m plant ticks of dt that TRACK it (queued, not waited for): per range, on the range's stream,
+            1. Optimization::Step on the plant's state x0, as tick() makes it;
+            2. the nominal trajectory of the plan's first m controls from x0, sim_rollout_states with the CONTROLLER's
+               parameters `dyn` and the plant's tick map (1 ms sub-steps over dt), without the external forces;
+            3. sim_lqr along it with the state weights q (nx numbers), the control weight r and `terminal` (sim_lqr's: an
+               [nx, nx, B] tensor, nx numbers, or None: diag(q));
+            4. BatchSimulator.rollout_feedback on the plants (plant_dyn, else dyn) under u_k + K[k] . wrap(x - x_nom_k),
+               clamped to the handle's u_limit -- one launch for the m ticks;
+            5. the warm start's controls shifted by m - 1 more places, the last one duplicated: the next step's own shift by
+               one then starts from u_m, and its u_prev is u_{m-1}, the last nominal control applied.
+        ticks advances by m.  m = 1 leaves the plants and the warm start bitwise as tick() does (the deviation from the
+        nominal start is exactly 0).  1 <= m <= window_length.  The gains belong to the plant's map at dt, not to the
+        controller's RK4 at control_dt; there is no feedback inside a tick, and the Riccati recursion does not know of the
+        clamp.  fext: optional callable (range index) -> [4, n] tensor of external forces on that range's plants, the same
+        for the m ticks; the nominal trajectory does not see them.  dyn, plant_dyn, set_point as tick()'s.  Not for
+        feedback=True loops: their gain is the QP's du_0/dx0 applied at sub-step rate, another law for the same ticks."""
+        if self.feedback:
+            raise ValueError("ClosedLoop.tick_hold: the loop was made with feedback=True, whose tick() applies the QP's own "
+                             "gain; make the loop with feedback=False to track with the Riccati gains")
+        m = int(m)
+        if not 1 <= m <= self.opts[0].N:
+            raise ValueError("m must be in [1, window_length = %d]" % self.opts[0].N)
+        if isinstance(dyn, torch.Tensor) and plant_dyn is None:
+            raise TypeError("ClosedLoop.tick_hold: dyn is the plant's parameter set too: pass the %d numbers, not a tensor, or "
+                            "give plant_dyn" % self.sims[0].np)
+        tensors = [t for t in (set_point, plant_dyn, dyn, terminal) if isinstance(t, torch.Tensor)]
+        if len(self.sims) > 1 and (self._inputs_dirty or tensors):
+            cur = torch.cuda.current_stream(self.device)   # as tick(): what prepared the inputs on the caller's stream comes first
+            for st in self.streams:
+                st.wait_stream(cur)
+                for t in tensors:
+                    t.record_stream(st)
+            self._inputs_dirty = False
+        one = len(self.sims) == 1
+
+        def cols(t, lo, hi):   # this range's columns of a per-problem tensor [..., B]
+            return t if one or not isinstance(t, torch.Tensor) else t[..., lo:hi].contiguous()
+        for i, (s, o, out) in enumerate(zip(self.sims, self.opts, self.outs)):
+            lo, hi = self.bounds[i], self.bounds[i + 1]
+            with self._on(i):
+                dyn_i = cols(dyn, lo, hi)
+                pd = dyn_i if plant_dyn is None else cols(plant_dyn, lo, hi)
+                x0 = s.get_state()   # rollout_feedback gives the plant a new tensor: this one stays the plan's x0
+                res = o.step(x0, dyn_i, cols(set_point, lo, hi), want_predicted=False, want_stats=want_stats, out=out)
+                u_nom = res.u[:m]
+                xs_nom = sim_rollout_states(dyn_i, dt, x0, u_nom, model=self.model)["xs"]
+                K = sim_lqr(dyn_i, dt, x0, u_nom, xs_nom, q, r, terminal=cols(terminal, lo, hi), model=self.model, want="K")["K"]
+                s.rollout_feedback(pd, dt, u_nom, K, x0, xs_nom, u_limit=self.u_limit, fext=None if fext is None else fext(i))
+                if m > 1:
+                    n = hi - lo
+                    z = o.get_solution(n)
+                    zu = z[o.dim - o.N:]
+                    z[o.dim - o.N:] = torch.cat([zu[m - 1:], zu[-1:].expand(m - 1, n)])
+                    o.set_previous_solution(z)
+        self.ticks += m
 
     def _tick_feedback(self, i, s, o, out, dyn, sp, dt, want_stats, substeps, fext, sp_inner=None, plant_dyn=None):
         plant_dyn = dyn if plant_dyn is None else plant_dyn   # the plants' parameters (tick: plant_dyn)

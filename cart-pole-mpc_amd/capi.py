@@ -52,6 +52,7 @@ SYMBOLS = [
     "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
     "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch", "cpmpc_sim_rollout_gn_batch",
     "cpmpc_sim_rollout_gn_x0_batch", "cpmpc_sim_ekf_batch", "cpmpc_sim_rts_batch", "cpmpc_sim_rts_work_rows",
+    "cpmpc_sim_lqr_batch", "cpmpc_sim_rollout_fb_batch",
 ]
 
 
@@ -384,6 +385,48 @@ class SimRts(C.Structure):
     ]
 
 
+class SimLqr(C.Structure):
+    """cpmpc_sim_lqr: device pointers of cpmpc_sim_lqr_batch; the trajectory x0, u [T][B], xs (a forward call's), dyn and the
+    terminal cost PT (its lower triangle) are read, q_host (state weights) and qf_host (terminal weights where PT is null) are
+    NX host doubles each, r is the control weight, K and P0 are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("xs", C.c_void_p),
+        ("q_host", C.POINTER(C.c_double)),
+        ("r", C.c_double),
+        ("PT", C.c_void_p),
+        ("qf_host", C.POINTER(C.c_double)),
+        ("K", C.c_void_p),
+        ("P0", C.c_void_p),
+    ]
+
+
+class SimRolloutFb(C.Structure):
+    """cpmpc_sim_rollout_fb: device pointers of cpmpc_sim_rollout_fb_batch; x0, the nominal controls u_nom [T][B], the gains K,
+    the nominal trajectory x0_nom / xs_nom and dyn are read, u_limit is the clamp (infinity: none), xs, x_final and us (the
+    controls applied) are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u_nom", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("K", C.c_void_p),
+        ("x0_nom", C.c_void_p),
+        ("xs_nom", C.c_void_p),
+        ("u_limit", C.c_double),
+        ("xs", C.c_void_p),
+        ("x_final", C.c_void_p),
+        ("us", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -522,6 +565,8 @@ def load():
     L.cpmpc_sim_rts_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRts), vp]
     L.cpmpc_sim_rts_work_rows.argtypes = [i32, i32]
     L.cpmpc_sim_rts_work_rows.restype = i64
+    L.cpmpc_sim_lqr_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimLqr), vp]
+    L.cpmpc_sim_rollout_fb_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutFb), vp]
     _lib = L
     return L
 

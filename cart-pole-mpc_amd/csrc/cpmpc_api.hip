@@ -1176,6 +1176,71 @@ extern "C" int cpmpc_sim_rts_batch(int model, int dtype, int64_t B, const double
   });
 }
 
+// ---- tracking a plant trajectory: its LQR gains and the plant under them (sim_track_kernels.hpp) -----------------------
+static int check_sim_lqr_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                              const cpmpc_sim_lqr* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_lqr)");
+  int rc = check_rollout_common("cpmpc_sim_lqr", a->struct_size, sizeof(cpmpc_sim_lqr), a->x0, a->u, dyn_shared_host, a->dyn,
+                                dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->K && !a->P0) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (T > 1 && !a->xs) return fail(CPMPC_ERR_INVALID_ARG, "xs (a forward call's checkpoints) is required when T > 1");
+  if (!(a->r > 0.0) || !std::isfinite(a->r)) return fail(CPMPC_ERR_INVALID_ARG, "r must be finite and > 0");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  rc = check_host_weights("q_host", a->q_host, nx);
+  if (!rc) rc = check_host_weights("qf_host", a->qf_host, nx);
+  if (rc) return rc;
+  const ArraySpan outs[2] = {{a->K, nt * nx, "K"}, {a->P0, nx * nx, "P0"}};
+  const ArraySpan ins[6] = {{a->x0, nx, "x0"},     {a->u, nt, "u"},        {a->fext, 4, "fext"},
+                            {a->dyn, np, "dyn"},   {a->xs, nt * nx, "xs"}, {a->PT, nx * nx, "PT"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_lqr_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                   const cpmpc_sim_lqr* a, void* stream) {
+  int rc = check_sim_lqr_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_lqr(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
+static int check_sim_rollout_fb_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                     const cpmpc_sim_rollout_fb* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout_fb)");
+  int rc = check_struct_size("cpmpc_sim_rollout_fb", a->struct_size, sizeof(cpmpc_sim_rollout_fb));
+  if (rc) return rc;
+  if (!a->u_nom) return fail(CPMPC_ERR_INVALID_ARG, "null argument (u_nom)");
+  rc = check_rollout_common("cpmpc_sim_rollout_fb", a->struct_size, sizeof(cpmpc_sim_rollout_fb), a->x0, a->u_nom,
+                            dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->xs && !a->x_final && !a->us) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (!(a->u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no clamp)");
+  if (a->K && !a->x0_nom) return fail(CPMPC_ERR_INVALID_ARG, "K is given without x0_nom");
+  if (a->K && T > 1 && !a->xs_nom)
+    return fail(CPMPC_ERR_INVALID_ARG, "K is given without xs_nom (the nominal checkpoints), required when T > 1");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  const ArraySpan outs[3] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}, {a->us, nt, "us"}};
+  // the nominal trajectory is read only where K is given
+  const ArraySpan ins[7] = {{a->x0, nx, "x0"},
+                            {a->u_nom, nt, "u_nom"},
+                            {a->fext, 4, "fext"},
+                            {a->dyn, np, "dyn"},
+                            {a->K, nt * nx, "K"},
+                            {a->K ? a->x0_nom : nullptr, nx, "x0_nom"},
+                            {a->K ? a->xs_nom : nullptr, nt * nx, "xs_nom"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_rollout_fb_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                          const cpmpc_sim_rollout_fb* a, void* stream) {
+  int rc = check_sim_rollout_fb_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_rollout_fb(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

@@ -245,6 +245,14 @@ struct Engine {
   // that are not null
   void (*sim_rts)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_rts* a,
                   hipStream_t stream);
+  // the backward Riccati recursion along a plant trajectory in one launch: K, P0 of `a` that are not null
+  // (sim_track_kernels.hpp)
+  void (*sim_lqr)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_lqr* a,
+                  hipStream_t stream);
+  // T ticks of the plant under u_nom[t] + K[t] . wrap(x_t - x_nom_t), clamped, in one launch: xs, x_final, us of `a` that are
+  // not null (sim_track_kernels.hpp)
+  void (*sim_rollout_fb)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                         const cpmpc_sim_rollout_fb* a, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -733,6 +733,91 @@ int64_t cpmpc_sim_rts_work_rows(int model, int T);
 int cpmpc_sim_rts_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                         const cpmpc_sim_rts* a, void* stream);
 
+/* ---- tracking a plant trajectory between two re-plans: its LQR gains, and the plant under them, one launch each ---- */
+/* The TIME-VARYING LQR GAINS along a plant trajectory in one launch: the backward Riccati recursion of the cost
+ *     sum_{t<T} (d_t^T diag(q_host) d_t + r du_t^2) + d_T^T P_T d_T        d_t = x_t - x_nom_t, du_t = u_t - u_nom[t]
+ * linearised along the trajectory x0, u [T][B], xs [T][NX][B] -- a cpmpc_sim_rollout_batch call's on the same inputs,
+ * required when T > 1; row T-1 is never read.  The plant has one input, so no matrix is inverted.  Reverse over the ticks,
+ * forward inside a tick: with x_t = (t == 0) ? x0 : xs[t-1] and Phi_t = dx+/dx, gamma_t = dx+/du of the tick at (x_t, u[t])
+ * as cpmpc_sim_step_jac_batch's A and Bu,
+ *     P = P_T
+ *     for t = T-1 .. 0:
+ *         v   = P gamma_t
+ *         s   = r + gamma_t . v
+ *         k_t = -(Phi_t^T v) / s
+ *         Acl = Phi_t + gamma_t k_t^T
+ *         P   = diag(q_host) + r k_t k_t^T + Acl^T P Acl
+ *     P0 = P
+ * SIGN CONVENTION: K[t] = k_t is applied as u_t = u_nom[t] + k_t . (x_t - x_nom_t) -- what cpmpc_sim_rollout_fb_batch does
+ * -- and d^T P0 d is the cost-to-go of a deviation d at the window's start.  The update is the Joseph-like form: a sum of
+ * positive semidefinite terms, so P stays positive semidefinite in rounded arithmetic.  Only P's lower triangle is computed.
+ * P_T is PT [NX*NX][B] (element (j, k) at field j*NX + k; ONLY THE LOWER TRIANGLE, k <= j, IS READ: a call's P0 chains
+ * windows, and T1 + T2 ticks are bitwise the T2-tick tail's P0 given as PT to the T1-tick head), else diag(qf_host), else
+ * diag(q_host).  q_host: NX weights >= 0, NULL: ones.  r: finite and > 0.
+ *     K [T][NX][B], row t the gain of tick t;   P0 [NX*NX][B], full and exactly symmetric.
+ * Each output is nullable, at least one must be given, and each is bitwise the same whether or not the other is asked for.
+ * The gains belong to the PLANT's map at dt (its sub-steps of 1 ms, the control held over the tick), not to a controller's
+ * model of it.  dt = 0: K = 0 and P0 = P_T + T diag(q_host).  NOT modelled: a clamp of the control, feedback inside a tick,
+ * cross terms of the cost.  No output may overlap x0, u, xs, fext, dyn or PT.  A problem with non-finite data has non-finite
+ * outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size, r not finite and > 0, a negative or non-finite q_host or qf_host entry, xs == NULL with T > 1 and the
+ * pointer rules above -> CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_lqr {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_lqr) */
+  const void* x0;         /* [NX][B], read only: the start of the trajectory */
+  const void* u;          /* [T][B] the trajectory's controls */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* xs;         /* [T][NX][B]: a forward call's; required when T > 1 */
+  const double* q_host;   /* NX state weights >= 0, or NULL: ones */
+  double r;               /* the control weight, finite and > 0 */
+  const void* PT;         /* [NX*NX][B] terminal cost or NULL; the lower triangle is read */
+  const double* qf_host;  /* NX terminal weights >= 0 used where PT is NULL, or NULL: q_host's */
+  void* K;                /* [T][NX][B] or NULL */
+  void* P0;               /* [NX*NX][B] or NULL */
+} cpmpc_sim_lqr;
+int cpmpc_sim_lqr_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                        const cpmpc_sim_lqr* a, void* stream);
+
+/* The plant under an AFFINE FEEDBACK LAW for T ticks in one launch: cpmpc_sim_rollout_batch's loop with the tick's control
+ * formed on the device at the tick's start and held over its sub-steps,
+ *     d   = wrap(x_t - x_nom_t)                       x_nom_0 = x0_nom, x_nom_t = xs_nom[t-1]; pole angles to the nearest turn
+ *     u_t = clamp(u_nom[t] + K[t] . d, +-u_limit)
+ *     x_{t+1} = Step(x_t, u_t, dt)
+ * SIGN CONVENTION: K [T][NX][B] is cpmpc_sim_lqr_batch's.  K == NULL: no feedback, u_t = clamp(u_nom[t]), and the nominal
+ * trajectory is not read.  x0_nom [NX][B] is required where K is given, xs_nom [T][NX][B] also when T > 1; row T-1 of xs_nom
+ * is never read.  u_limit > 0; +infinity: no clamp.  The parameters and forces are THE CALL'S OWN and may differ from those
+ * the nominal trajectory and the gains were made with (model mismatch).
+ *     xs [T][NX][B], x_final [NX][B], us [T][B] the controls applied;
+ * each is nullable and at least one must be given; each is bitwise the same whichever others are asked for.  Two identities
+ * hold BITWISE: with K == NULL and u_limit = +infinity, xs and x_final are cpmpc_sim_rollout_batch's on u_nom; with
+ * x0 == x0_nom, the nominal trajectory's parameters, finite K and non-zero u_nom, d is exactly 0 at every tick and the call
+ * reproduces the nominal rollout.  There is NO feedback inside a tick, and cpmpc_sim_lqr_batch does not know of the clamp.
+ * No output may overlap x0, u_nom, K, x0_nom, xs_nom, fext or dyn.  A problem with non-finite data has non-finite outputs;
+ * no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1,
+ * a wrong struct_size, u_limit not > 0, K without x0_nom (or without xs_nom when T > 1) and the pointer rules above ->
+ * CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_rollout_fb {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_rollout_fb) */
+  const void* x0;         /* [NX][B], read only */
+  const void* u_nom;      /* [T][B] the nominal controls */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* K;          /* [T][NX][B] gains or NULL: no feedback */
+  const void* x0_nom;     /* [NX][B] the nominal start; required where K is given */
+  const void* xs_nom;     /* [T][NX][B] the nominal checkpoints; required where K is given and T > 1 */
+  double u_limit;         /* > 0; +infinity: no clamp */
+  void* xs;               /* [T][NX][B] or NULL */
+  void* x_final;          /* [NX][B] or NULL */
+  void* us;               /* [T][B] or NULL */
+} cpmpc_sim_rollout_fb;
+int cpmpc_sim_rollout_fb_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                               const cpmpc_sim_rollout_fb* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
