@@ -1459,6 +1459,202 @@ def sim_rollout_feedback(params, dt, state, u_nom, K, x0_nom, xs_nom, u_limit=fl
     return res
 
 
+def _ilqr_reference(x_ref, T, nx, B, dtype, device):
+    """x_ref -> a contiguous [T + 1, nx, B] tensor: row 0 the target of the start, row t of the state after tick t - 1 (row T
+    the terminal target).  [T + 1, nx, B] is taken as it is; nx numbers (or an [nx] tensor) and [nx, B] are a constant target,
+    expanded."""
+    if not isinstance(x_ref, torch.Tensor):
+        x_ref = torch.tensor([float(v) for v in x_ref], dtype=dtype, device=device)
+    _require_cuda_tensor(x_ref, "x_ref", dtype, contiguous=False)
+    if x_ref.shape == (T + 1, nx, B):
+        return x_ref if x_ref.is_contiguous() else x_ref.contiguous()
+    if x_ref.shape == (nx,):
+        return x_ref.reshape(1, nx, 1).expand(T + 1, nx, B).contiguous()
+    if x_ref.shape == (nx, B):
+        return x_ref.reshape(1, nx, B).expand(T + 1, nx, B).contiguous()
+    raise ValueError("x_ref must be [T + 1, %d, B] = [%d, %d, %d], [%d, B] or %d numbers" % (nx, T + 1, nx, B, nx, nx))
+
+
+def _ilqr_cost(a, nx, B, T, dtp, device, x_ref, u_ref, q, terminal):
+    """The cost's fields of the two iLQR structs (reference, weights, terminal cost) set on `a` -> what must stay alive until
+    the call has returned."""
+    ref = _ilqr_reference(x_ref, T, nx, B, dtp, device)
+    a.x0_ref = ref[0].data_ptr()
+    a.xs_ref = ref[1:].data_ptr()
+    held = [ref]
+    if u_ref is not None:
+        _require_cuda_tensor(u_ref, "u_ref", dtp, (T, B))
+        a.u_ref = u_ref.data_ptr()
+    if q is not None:
+        q_host = capi.dbl_array(q, nx)   # read by the call itself, before it returns
+        a.q_host = C.cast(q_host, C.POINTER(C.c_double))
+        held.append(q_host)
+    if isinstance(terminal, torch.Tensor):
+        _require_cuda_tensor(terminal, "terminal", dtp, (nx, nx, B))
+        a.PT = terminal.data_ptr()
+    elif terminal is not None:
+        qf_host = capi.dbl_array(terminal, nx)
+        a.qf_host = C.cast(qf_host, C.POINTER(C.c_double))
+        held.append(qf_host)
+    return held
+
+
+def sim_ilqr_backward(params, dt, state, u, xs, x_ref, u_ref, q, r, terminal=None, mu=None, u_limit=float("inf"), fext=None,
+                      f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single", want=("K", "kff", "dV")):
+    """The backward pass of one iLQR iteration on the plant's tick map in ONE launch (include/cpmpc.h:
+    cpmpc_sim_ilqr_backward_batch), along the trajectory state [nx, B], u [T, B], xs [T, nx, B] (a sim_ilqr_forward or
+    sim_rollout_states call's; None is allowed for T = 1) for the cost, with no factor 1/2,
+        J = sum_{t<T} (e_t^T diag(q) e_t + r (u_t - u_ref[t])^2) + e_T^T P_T e_T,    e_t = wrap(x_t - x_ref[t]).
+    x_ref: [T + 1, nx, B] (row T the terminal target), or [nx, B] / nx numbers for a constant target; u_ref [T, B] or None:
+    zeros; q, r and terminal as sim_lqr's; mu [B] >= 0 or None: the regularisation added to the control's curvature per
+    problem; u_limit > 0: the box limit, handled inside the recursion (the plant has one input: a scalar clamp, exact), with
+    no feedback on a control that sits on it.  Per tick, last to first, with g HALF the gradient of the cost-to-go:
+        v = P gamma,  s0 = r + gamma . v,  s = s0 + mu,  h = r (u_t - u_ref[t]) + gamma . g,
+        k_t = clamp(u_t - h / s) - u_t,  K_t = clamped ? 0 : -(Phi^T v) / s,  dV1 += 2 k_t h,  dV2 += k_t^2 s0,
+        Acl = Phi + gamma K_t^T,  g = q o e_t + r (u_t - u_ref[t] + k_t) K_t + Acl^T (g + v k_t),
+        P = diag(q) + r K_t K_t^T + Acl^T P Acl.
+
+    Returns a dict with the entries named in `want`,
+        "K"    [T, nx, B]  the gains, sim_lqr's convention,      "kff"  [T, B]  the feedforward terms k_t,
+        "dV"   [2, B]      alpha dV[0] + alpha^2 dV[1] is the predicted change of J for a step alpha,
+        "P0"   [nx, nx, B] and "g0" [nx, B]  the model's cost-to-go at the start, x^T P0 x + 2 g0 . x,
+        "hmax" [B]         max_t |k_t| (s0 + mu): 0 at a stationary trajectory.
+    With mu None and no limit, K and P0 are sim_lqr's; with x_ref the trajectory itself, kff and dV are exactly 0.  Gauss-Newton:
+    second-order terms of the dynamics are not modelled.  params, dt and the forces as sim_rollout_states'."""
+    names = ("K", "kff", "dV", "P0", "g0", "hmax")
+    want = _want_tuple(want, names)
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimIlqrBackward(struct_size=C.sizeof(capi.SimIlqrBackward), r=float(r), u_limit=float(u_limit))
+    B, T, host, _, _held = _plant_inputs(dims, state, u, params, fext, f_base, f_mass, a, ticks=True)
+    if xs is not None:
+        _require_cuda_tensor(xs, "xs", dtp, (T, nx, B))
+        a.xs = xs.data_ptr()
+    elif T > 1:
+        raise ValueError("xs (a forward call's) is required when T > 1")
+    _cost_held = _ilqr_cost(a, nx, B, T, dtp, state.device, x_ref, u_ref, q, terminal)
+    if mu is not None:
+        _require_cuda_tensor(mu, "mu", dtp, (B,))
+        a.mu = mu.data_ptr()
+    res = _alloc_outputs(a, want, {"K": ("K", (T, nx, B)), "kff": ("kff", (T, B)), "dV": ("dV", (2, B)),
+                                   "P0": ("P0", (nx, nx, B)), "g0": ("g0", (nx, B)), "hmax": ("hmax", (B,))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_ilqr_backward_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                             _stream_ptr()))
+    return res
+
+
+def sim_ilqr_forward(params, dt, state, u_nom, kff, K, x0_nom, xs_nom, x_ref, u_ref, q, r, terminal=None, alpha=None,
+                     u_limit=float("inf"), fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+                     want=("xs", "us", "cost")):
+    """The forward pass of one iLQR iteration in ONE launch (include/cpmpc.h: cpmpc_sim_ilqr_forward_batch): from
+    state [nx, B] (read, not changed), per tick
+        d = wrap(x_t - x_nom_t),  u_t = clamp(u_nom[t] + alpha kff[t] + K[t] . d, +-u_limit),  x_{t+1} = the plant's tick,
+    with the cost J of sim_ilqr_backward summed on the device over the states passed and the controls applied.  kff [T, B] and
+    K [T, nx, B] are sim_ilqr_backward's, each or None (K needs x0_nom [nx, B] and, for T > 1, xs_nom [T, nx, B], as
+    sim_rollout_feedback); alpha [B]: the step on kff per problem, None: 1.  x_ref, u_ref, q, r, terminal: the cost, as
+    sim_ilqr_backward's.  With kff and K None it is the plain clamped rollout with its cost.
+
+    Returns a dict with the entries named in `want`,
+        "xs" [T, nx, B],  "x_final" [nx, B],  "us" [T, B] the controls applied,  "cost" [B].
+    With kff, K None and no limit, xs is sim_rollout_states' bit for bit; from the nominal start with alpha = 0 the nominal xs,
+    us (a forward call's own) and cost come back bit for bit."""
+    want = _want_tuple(want, ("xs", "x_final", "us", "cost"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimIlqrForward(struct_size=C.sizeof(capi.SimIlqrForward), r=float(r), u_limit=float(u_limit))
+    B, T, host, _, _held = _plant_inputs(dims, state, u_nom, params, fext, f_base, f_mass, a, ticks=True, u_field="u_nom")
+    if kff is not None:
+        _require_cuda_tensor(kff, "kff", dtp, (T, B))
+        a.kff = kff.data_ptr()
+    if K is not None:
+        _require_cuda_tensor(K, "K", dtp, (T, nx, B))
+        a.K = K.data_ptr()
+        if x0_nom is None:
+            raise ValueError("x0_nom (the nominal start) is required where K is given")
+        if xs_nom is None and T > 1:
+            raise ValueError("xs_nom (the nominal trajectory) is required where K is given and T > 1")
+    if x0_nom is not None:
+        _require_cuda_tensor(x0_nom, "x0_nom", dtp, (nx, B))
+        a.x0_nom = x0_nom.data_ptr()
+    if xs_nom is not None:
+        _require_cuda_tensor(xs_nom, "xs_nom", dtp, (T, nx, B))
+        a.xs_nom = xs_nom.data_ptr()
+    if alpha is not None:
+        _require_cuda_tensor(alpha, "alpha", dtp, (B,))
+        a.alpha = alpha.data_ptr()
+    _cost_held = _ilqr_cost(a, nx, B, T, dtp, state.device, x_ref, u_ref, q, terminal)
+    res = _alloc_outputs(a, want, {"xs": ("xs", (T, nx, B)), "x_final": ("x_final", (nx, B)), "us": ("us", (T, B)),
+                                   "cost": ("cost", (B,))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_ilqr_forward_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                            _stream_ptr()))
+    return res
+
+
+ILQR_ARMIJO = 1e-4   # a step is accepted where the cost falls by at least this share of the model's prediction
+
+
+def sim_ilqr(params, dt, state, u_init, x_ref, q, r, terminal=None, u_ref=None, u_limit=float("inf"), iterations=10, trials=6,
+             mu_init=0.0, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
+    """Iterative LQR on the plant's own tick map, every problem in lock-step with its own line search and regularisation: fixed
+    counts, elementwise torch between the launches, NO host synchronisation.  From state [nx, B] and the controls
+    u_init [T, B] (clamped to +-u_limit by the first rollout), for the cost of sim_ilqr_backward:
+        the first trajectory and its cost J: sim_ilqr_forward without kff and K;
+        per iteration: ONE sim_ilqr_backward (with the problem's mu); then `trials` sim_ilqr_forward calls for the cost alone,
+        alpha starting at 1: a problem ACCEPTS where dV[0] alpha + dV[1] alpha^2 < 0 and J_try - J <= 1e-4 of that prediction,
+        and keeps its alpha from then on (it recomputes the same bits on the later trials); one that has not accepted halves
+        alpha, and after the last trial gets alpha = 0; one more sim_ilqr_forward with the final alpha gives every problem's
+        new trajectory -- a failed problem's is its old one bit for bit; mu: accepted -> mu / 10, and 0 once below 1e-6,
+        failed -> max(10 mu, 1e-3).
+    So J never increases on any problem.  A closing sim_ilqr_backward at the returned trajectory (with the returned mu) gives
+    the gains that track it and its stationarity measure.
+
+    Returns a dict: "u" [T, B], "xs" [T, nx, B], "K" [T, nx, B], "cost" [B], "cost_history" [iterations + 1, B] (row 0: of
+    u_init), "hmax" [B], "mu" [B], "accepted" [iterations, B] bool."""
+    iterations, trials = int(iterations), int(trials)
+    if iterations < 0 or trials < 1:
+        raise ValueError("iterations must be >= 0 and trials >= 1")
+    if not float(mu_init) >= 0.0:
+        raise ValueError("mu_init must be >= 0")
+    _, nx, _ = _model_dims(model)
+    _require_cuda_tensor(state, "state", state.dtype)
+    _require_cuda_tensor(u_init, "u_init", state.dtype)
+    if state.dim() != 2 or u_init.dim() != 2:
+        raise ValueError("state must be [%d, B] and u_init [T, B]" % nx)
+    T, B = u_init.shape
+    dtp, dev = state.dtype, state.device
+    ref = _ilqr_reference(x_ref, T, nx, B, dtp, dev)
+    cost_kw = dict(terminal=terminal, u_limit=u_limit, fext=fext, f_base=f_base, f_mass=f_mass, model=model)
+    first = sim_ilqr_forward(params, dt, state, u_init, None, None, None, None, ref, u_ref, q, r, want=("xs", "us", "cost"),
+                             **cost_kw)
+    u, xs, J = first["us"], first["xs"], first["cost"]
+    mu = torch.full((B,), float(mu_init), dtype=dtp, device=dev)
+    history, accepted = [J], []
+    for _ in range(iterations):
+        bw = sim_ilqr_backward(params, dt, state, u, xs, ref, u_ref, q, r, mu=mu, want=("K", "kff", "dV"), **cost_kw)
+        dV1, dV2 = bw["dV"][0], bw["dV"][1]
+        alpha = torch.ones((B,), dtype=dtp, device=dev)
+        done = torch.zeros((B,), dtype=torch.bool, device=dev)
+        for _ in range(trials):
+            J_try = sim_ilqr_forward(params, dt, state, u, bw["kff"], bw["K"], state, xs, ref, u_ref, q, r, alpha=alpha,
+                                     want="cost", **cost_kw)["cost"]
+            pred = dV1 * alpha + dV2 * alpha * alpha
+            done = done | ((pred < 0) & (J_try - J <= ILQR_ARMIJO * pred))
+            alpha = torch.where(done, alpha, 0.5 * alpha)
+        alpha = torch.where(done, alpha, torch.zeros_like(alpha))
+        fin = sim_ilqr_forward(params, dt, state, u, bw["kff"], bw["K"], state, xs, ref, u_ref, q, r, alpha=alpha,
+                               want=("xs", "us", "cost"), **cost_kw)
+        u, xs, J = fin["us"], fin["xs"], fin["cost"]
+        down = mu / 10.0
+        mu = torch.where(done, torch.where(down < 1e-6, torch.zeros_like(mu), down), torch.clamp(10.0 * mu, min=1e-3))
+        history.append(J)
+        accepted.append(done)
+    last = sim_ilqr_backward(params, dt, state, u, xs, ref, u_ref, q, r, mu=mu, want=("K", "hmax"), **cost_kw)
+    return {"u": u, "xs": xs, "K": last["K"], "cost": J, "cost_history": torch.stack(history), "hmax": last["hmax"], "mu": mu,
+            "accepted": torch.stack(accepted) if accepted else torch.zeros((0, B), dtype=torch.bool, device=dev)}
+
+
 def _full_covariance(cov, nx, batch, dtype, name):
     """cov [nx, B] (a diagonal) or [nx, nx, B] -> a fresh [nx, nx, B] tensor"""
     _require_cuda_tensor(cov, name, dtype)
@@ -1697,6 +1893,13 @@ class BatchSimulator:
                                    want=("xs", "x_final", "us"))
         self.state = res["x_final"]
         return res["xs"], res["us"]
+
+    def ilqr(self, params, dt, u_init, x_ref, q, r, terminal=None, u_ref=None, u_limit=float("inf"), iterations=10, trials=6,
+             mu_init=0.0, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
+        """sim_ilqr from the simulator's own state, which is read and NOT advanced: a plan for the T ticks ahead (its dict)."""
+        return sim_ilqr(params.detach() if isinstance(params, torch.Tensor) else params, dt, self.state, u_init, x_ref, q, r,
+                        terminal=terminal, u_ref=u_ref, u_limit=u_limit, iterations=iterations, trials=trials, mu_init=mu_init,
+                        fext=fext, f_base=f_base, f_mass=f_mass, model=self.model)
 
     def rollout_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """rollout() with a backward: xs = sim_rollout(params, dt, self.state, u, ...) is returned, attached to the autograd

@@ -52,7 +52,7 @@ SYMBOLS = [
     "cpmpc_sim_step_dyn_batch", "cpmpc_sim_step_param_jac_batch", "cpmpc_sim_step_param_jac_batch_host",
     "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch", "cpmpc_sim_rollout_gn_batch",
     "cpmpc_sim_rollout_gn_x0_batch", "cpmpc_sim_ekf_batch", "cpmpc_sim_rts_batch", "cpmpc_sim_rts_work_rows",
-    "cpmpc_sim_lqr_batch", "cpmpc_sim_rollout_fb_batch",
+    "cpmpc_sim_lqr_batch", "cpmpc_sim_rollout_fb_batch", "cpmpc_sim_ilqr_backward_batch", "cpmpc_sim_ilqr_forward_batch",
 ]
 
 
@@ -427,6 +427,68 @@ class SimRolloutFb(C.Structure):
     ]
 
 
+class SimIlqrBackward(C.Structure):
+    """cpmpc_sim_ilqr_backward: device pointers of cpmpc_sim_ilqr_backward_batch; the trajectory x0, u [T][B], xs, the reference
+    x0_ref, xs_ref (row T-1: the terminal target), u_ref (null: zeros), dyn, PT (its lower triangle) and mu [B] are read;
+    q_host, qf_host and r as cpmpc_sim_lqr's; u_limit is the box limit (infinity: none); K, kff, dV, P0, g0 and hmax are
+    nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("xs", C.c_void_p),
+        ("x0_ref", C.c_void_p),
+        ("xs_ref", C.c_void_p),
+        ("u_ref", C.c_void_p),
+        ("q_host", C.POINTER(C.c_double)),
+        ("r", C.c_double),
+        ("PT", C.c_void_p),
+        ("qf_host", C.POINTER(C.c_double)),
+        ("mu", C.c_void_p),
+        ("u_limit", C.c_double),
+        ("K", C.c_void_p),
+        ("kff", C.c_void_p),
+        ("dV", C.c_void_p),
+        ("P0", C.c_void_p),
+        ("g0", C.c_void_p),
+        ("hmax", C.c_void_p),
+    ]
+
+
+class SimIlqrForward(C.Structure):
+    """cpmpc_sim_ilqr_forward: device pointers of cpmpc_sim_ilqr_forward_batch; x0, the nominal controls u_nom [T][B], kff, K,
+    the nominal trajectory x0_nom / xs_nom, the per-problem step alpha [B] (null: 1), the reference, dyn and PT are read;
+    u_limit is the clamp (infinity: none); xs, x_final, us (the controls applied) and cost are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u_nom", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("kff", C.c_void_p),
+        ("K", C.c_void_p),
+        ("x0_nom", C.c_void_p),
+        ("xs_nom", C.c_void_p),
+        ("alpha", C.c_void_p),
+        ("u_limit", C.c_double),
+        ("x0_ref", C.c_void_p),
+        ("xs_ref", C.c_void_p),
+        ("u_ref", C.c_void_p),
+        ("q_host", C.POINTER(C.c_double)),
+        ("r", C.c_double),
+        ("PT", C.c_void_p),
+        ("qf_host", C.POINTER(C.c_double)),
+        ("xs", C.c_void_p),
+        ("x_final", C.c_void_p),
+        ("us", C.c_void_p),
+        ("cost", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -567,6 +629,8 @@ def load():
     L.cpmpc_sim_rts_work_rows.restype = i64
     L.cpmpc_sim_lqr_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimLqr), vp]
     L.cpmpc_sim_rollout_fb_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutFb), vp]
+    L.cpmpc_sim_ilqr_backward_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimIlqrBackward), vp]
+    L.cpmpc_sim_ilqr_forward_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimIlqrForward), vp]
     _lib = L
     return L
 

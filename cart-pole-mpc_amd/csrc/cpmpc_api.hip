@@ -1241,6 +1241,94 @@ extern "C" int cpmpc_sim_rollout_fb_batch(int model, int dtype, int64_t B, const
   });
 }
 
+// ---- iterative LQR on the plant's tick map: the backward and the forward pass (sim_ilqr_kernels.hpp) ---------------------
+// what the two calls share beyond check_rollout_common: the cost's weights, the limit and the reference
+template <typename Args>
+static int check_sim_ilqr_cost(const Args* a, size_t nx) {
+  if (!(a->r > 0.0) || !std::isfinite(a->r)) return fail(CPMPC_ERR_INVALID_ARG, "r must be finite and > 0");
+  int rc = check_host_weights("q_host", a->q_host, nx);
+  if (!rc) rc = check_host_weights("qf_host", a->qf_host, nx);
+  if (rc) return rc;
+  if (!(a->u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no limit)");
+  if (!a->x0_ref || !a->xs_ref)
+    return fail(CPMPC_ERR_INVALID_ARG, "null argument (x0_ref, xs_ref: the reference; row T-1 of xs_ref is the terminal target)");
+  return CPMPC_OK;
+}
+
+static int check_sim_ilqr_backward_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                        const cpmpc_sim_ilqr_backward* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_ilqr_backward)");
+  int rc = check_rollout_common("cpmpc_sim_ilqr_backward", a->struct_size, sizeof(cpmpc_sim_ilqr_backward), a->x0, a->u,
+                                dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->K && !a->kff && !a->dV && !a->P0 && !a->g0 && !a->hmax)
+    return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (T > 1 && !a->xs) return fail(CPMPC_ERR_INVALID_ARG, "xs (a forward call's checkpoints) is required when T > 1");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  rc = check_sim_ilqr_cost(a, nx);
+  if (rc) return rc;
+  const ArraySpan outs[6] = {{a->K, nt * nx, "K"},     {a->kff, nt, "kff"}, {a->dV, 2, "dV"},
+                             {a->P0, nx * nx, "P0"},   {a->g0, nx, "g0"},   {a->hmax, 1, "hmax"}};
+  const ArraySpan ins[10] = {{a->x0, nx, "x0"},         {a->u, nt, "u"},
+                             {a->fext, 4, "fext"},      {a->dyn, np, "dyn"},
+                             {a->xs, nt * nx, "xs"},    {a->x0_ref, nx, "x0_ref"},
+                             {a->xs_ref, nt * nx, "xs_ref"}, {a->u_ref, nt, "u_ref"},
+                             {a->PT, nx * nx, "PT"},    {a->mu, 1, "mu"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_ilqr_backward_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt,
+                                             int T, const cpmpc_sim_ilqr_backward* a, void* stream) {
+  int rc = check_sim_ilqr_backward_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_ilqr_backward(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
+static int check_sim_ilqr_forward_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                       const cpmpc_sim_ilqr_forward* a) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_ilqr_forward)");
+  int rc = check_struct_size("cpmpc_sim_ilqr_forward", a->struct_size, sizeof(cpmpc_sim_ilqr_forward));
+  if (rc) return rc;
+  if (!a->u_nom) return fail(CPMPC_ERR_INVALID_ARG, "null argument (u_nom)");
+  rc = check_rollout_common("cpmpc_sim_ilqr_forward", a->struct_size, sizeof(cpmpc_sim_ilqr_forward), a->x0, a->u_nom,
+                            dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->xs && !a->x_final && !a->us && !a->cost) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  rc = check_sim_ilqr_cost(a, nx);
+  if (rc) return rc;
+  if (a->K && !a->x0_nom) return fail(CPMPC_ERR_INVALID_ARG, "K is given without x0_nom");
+  if (a->K && T > 1 && !a->xs_nom)
+    return fail(CPMPC_ERR_INVALID_ARG, "K is given without xs_nom (the nominal checkpoints), required when T > 1");
+  const ArraySpan outs[4] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}, {a->us, nt, "us"}, {a->cost, 1, "cost"}};
+  // the nominal trajectory is read only where K is given
+  const ArraySpan ins[13] = {{a->x0, nx, "x0"},
+                             {a->u_nom, nt, "u_nom"},
+                             {a->fext, 4, "fext"},
+                             {a->dyn, np, "dyn"},
+                             {a->kff, nt, "kff"},
+                             {a->K, nt * nx, "K"},
+                             {a->K ? a->x0_nom : nullptr, nx, "x0_nom"},
+                             {a->K ? a->xs_nom : nullptr, nt * nx, "xs_nom"},
+                             {a->alpha, 1, "alpha"},
+                             {a->x0_ref, nx, "x0_ref"},
+                             {a->xs_ref, nt * nx, "xs_ref"},
+                             {a->u_ref, nt, "u_ref"},
+                             {a->PT, nx * nx, "PT"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_ilqr_forward_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                            const cpmpc_sim_ilqr_forward* a, void* stream) {
+  int rc = check_sim_ilqr_forward_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_ilqr_forward(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

@@ -253,6 +253,14 @@ struct Engine {
   // not null (sim_track_kernels.hpp)
   void (*sim_rollout_fb)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                          const cpmpc_sim_rollout_fb* a, hipStream_t stream);
+  // one iLQR backward pass along a plant trajectory in one launch: K, kff, dV, P0, g0, hmax of `a` that are not null
+  // (sim_ilqr_kernels.hpp)
+  void (*sim_ilqr_backward)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                            const cpmpc_sim_ilqr_backward* a, hipStream_t stream);
+  // T ticks of the plant under u_nom[t] + alpha kff[t] + K[t] . wrap(x_t - x_nom_t), clamped, with the cost summed, in one
+  // launch: xs, x_final, us, cost of `a` that are not null (sim_ilqr_kernels.hpp)
+  void (*sim_ilqr_forward)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                           const cpmpc_sim_ilqr_forward* a, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -23,6 +23,7 @@
 #include "sim_ekf_kernels.hpp"
 #include "sim_rts_kernels.hpp"
 #include "sim_track_kernels.hpp"
+#include "sim_ilqr_kernels.hpp"
 
 using namespace cpmpc;
 
@@ -677,6 +678,39 @@ static void sim_rollout_fb_impl(int64_t B, const double* dyn_shared_host, int n_
   });
 }
 
+// ---- one iLQR iteration on the plant's tick map: the backward and the forward pass, one launch each (sim_ilqr_kernels.hpp) ----
+// the terminal diagonal where PT is NULL: qf_host, else q_host, else ones -- sim_lqr_impl's rule
+template <typename R, typename M>
+static void sim_ilqr_backward_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                                   const cpmpc_sim_ilqr_backward* a, hipStream_t stream) {
+  const StateWeights<R, M::NX> q = state_weights<R, M::NX>(a->q_host, 1.0),
+                               qf = state_weights<R, M::NX>(a->qf_host ? a->qf_host : a->q_host, 1.0);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    hipLaunchKernelGGL((sim_ilqr_backward_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                       plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u, (const R*)a->xs, (const R*)a->x0_ref,
+                       (const R*)a->xs_ref, (const R*)a->u_ref, q, (R)a->r, (const R*)a->PT, qf, (const R*)a->mu,
+                       (R)a->u_limit, (R*)a->K, (R*)a->kff, (R*)a->dV, (R*)a->P0, (R*)a->g0, (R*)a->hmax);
+  });
+}
+
+template <typename R, typename M>
+static void sim_ilqr_forward_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                                  const cpmpc_sim_ilqr_forward* a, hipStream_t stream) {
+  const StateWeights<R, M::NX> q = state_weights<R, M::NX>(a->q_host, 1.0),
+                               qf = state_weights<R, M::NX>(a->qf_host ? a->qf_host : a->q_host, 1.0);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    hipLaunchKernelGGL((sim_ilqr_forward_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                       plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u_nom, (const R*)a->kff, (const R*)a->K,
+                       (const R*)a->x0_nom, (const R*)a->xs_nom, (const R*)a->alpha, (R)a->u_limit, (const R*)a->x0_ref,
+                       (const R*)a->xs_ref, (const R*)a->u_ref, q, (R)a->r, (const R*)a->PT, qf, (R*)a->xs, (R*)a->x_final,
+                       (R*)a->us, (R*)a->cost);
+  });
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize (a caller's z goes through the
 // step buffers dzx / dzu, which hold no state between calls; z == NULL: the warm start itself, read only), then one lane
@@ -820,7 +854,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
 // swapped unseen, and the order of engine.hpp's declarations is free.  A new member gets a line here.
 #define CPMPC_DEFINE_ENGINE(NAME, R, M)                                                                               \
   const Engine* NAME() {                                                                                              \
-    static_assert(sizeof(Engine) == 27 * sizeof(void*), "an entry point of engine.hpp has no line below");            \
+    static_assert(sizeof(Engine) == 29 * sizeof(void*), "an entry point of engine.hpp has no line below");            \
     static const Engine e = [] {                                                                                      \
       Engine t{};                                                                                                     \
       t.step_batch = &step_batch_impl<R, M>;              t.host_chunk_begin = &host_chunk_begin<R, M>;               \
@@ -836,7 +870,8 @@ static int debug_read_impl(int which, unsigned long long* out) {
       t.sim_rollout_vjp = &sim_rollout_vjp_impl<R, M>;    t.sim_rollout_gn = &sim_rollout_gn_impl<R, M>;              \
       t.sim_rollout_gn_x0 = &sim_rollout_gn_x0_impl<R, M>; t.sim_ekf = &sim_ekf_impl<R, M>;                           \
       t.sim_rts = &sim_rts_impl<R, M>;                    t.sim_lqr = &sim_lqr_impl<R, M>;                            \
-      t.sim_rollout_fb = &sim_rollout_fb_impl<R, M>;                                                                  \
+      t.sim_rollout_fb = &sim_rollout_fb_impl<R, M>;      t.sim_ilqr_backward = &sim_ilqr_backward_impl<R, M>;        \
+      t.sim_ilqr_forward = &sim_ilqr_forward_impl<R, M>;                                                              \
       return t;                                                                                                       \
     }();                                                                                                              \
     return &e;                                                                                                        \

@@ -1,0 +1,342 @@
+// sim_ilqr_kernels.hpp -- one iteration of an iterative LQR on the plant's own tick map, as two kernels: the backward Riccati
+// pass with a feedforward term, the exact treatment of the control's box limit and the predicted cost change; and the forward
+// pass that applies alpha . k_t and sums the cost on the device.  The plant has ONE input, so the box QP of control-limited DDP
+// is a scalar clamp and, as in sim_lqr_kernel (sim_track_kernels.hpp), no matrix is inverted.
+//
+// The cost, sim_lqr's convention with no factor 1/2: with e_t = wrap_residual(x_t - xref_t), x_0 = x0, x_t = xs[t-1],
+// xref_0 = x0_ref, xref_t = xs_ref[t-1] (row T-1 of xs_ref IS read: it is the terminal target),
+//     J = sum_{t<T} (e_t^T diag(q) e_t + r (u_t - uref_t)^2) + e_T^T P_T e_T
+//
+// sim_ilqr_backward_kernel: sim_lqr_kernel's walk -- REVERSE over the ticks, FORWARD inside a tick, Phi_t and gamma_t from
+// sim_jac_tick.inc at (x_t, u[t]) -- with g, HALF the gradient of the cost-to-go, carried beside P:
+//     P = P_T ;  g = P_T e_T ;  dV1 = dV2 = 0 ;  hmax = 0
+//     for t = T-1 .. 0:
+//         v   = P gamma_t ;  s0 = r + gamma_t . v ;  s = s0 + mu            mu >= 0 per lane, NULL: 0
+//         h   = r (u_t - uref_t) + gamma_t . g
+//         k   = clamp(u_t - h / s, +-u_limit) - u_t                          -> kff[t]
+//         K_t = (the clamp changed u_t - h / s) ? 0 : -(Phi_t^T v) / s        -> K[t]
+//         dV1 += 2 k h ;  dV2 += k^2 s0 ;  hmax = max(hmax, |k| s)
+//         Acl = Phi_t + gamma_t K_t^T
+//         g   = q o e_t + r (u_t - uref_t + k) K_t + Acl^T (g + v k)
+//         P   = diag(q) + r K_t K_t^T + Acl^T P Acl                           the lower triangle only, as sim_lqr_kernel
+//     P0 = P ;  g0 = g
+// alpha dV1 + alpha^2 dV2 is the predicted change of J for a step alpha.  The P and g updates are the cost of the affine policy
+// du = k + K_t dx in the linear-quadratic model and hold for ANY k and K_t, so P stays a sum of positive semidefinite terms
+// under mu and under the clamp.  With mu NULL and no limit the P and K arithmetic is sim_lqr_kernel's, statement for statement.
+// x_T is xs[T-1]; where xs is NULL (allowed for T == 1) it is rolled from x0 by plant_sub_step, the rollout's own function.
+// P's triangle, g, and the three running sums live in lane-private LDS, acc[field][threadIdx.x], while the sub-step loop runs:
+// what is live there is sim_jac_kernel's set; x_t is loaded again after the tick for e_t.  Everything is computed whichever
+// outputs are stored (wave-uniform pointer tests).  n_sub == 0 is the identity plant with gamma = 0: K_t = 0,
+// k = clamp(u - (u - uref) r / (r + mu)) - u, g += q o e_t, P += diag(q), written as that.  Not modelled: second-order terms of
+// the dynamics (this is Gauss-Newton), cross terms of the cost, feedback inside a tick.
+//
+// sim_ilqr_forward_kernel: sim_rollout_fb_kernel's loop with a per-lane step on the feedforward term and the cost summed,
+//     u_t = clamp(u_nom[t] + alpha[p] kff[t] + K[t] . wrap_residual(x_t - x_nom_t), +-u_limit)
+//     x_{t+1} = Step(x_t, u_t, dt)                                            plant_sub_step, unchanged
+//     cost = J of (x0, xs, us) against the reference
+// kff and K are each nullable; with both NULL and u_limit = +inf it is sim_rollout_kernel bit for bit, with its cost.  alpha
+// NULL means 1.  From the nominal start with alpha = 0 the deviation is exactly 0 at every tick and the nominal controls (a
+// forward call's own, already inside the limit) and states come back bit for bit.
+#pragma once
+#include "sim_track_kernels.hpp"
+
+namespace cpmpc {
+
+// e^T P e with P's lower triangle in Pm (tri), or sum qf e^2 where there is no tensor
+template <typename R, int NX>
+__device__ __forceinline__ R ilqr_quad_tri(const R (&Pm)[tri(NX, 0)], const R (&e)[NX]) {
+  R a = R(0);
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    R row = R(0);
+#pragma unroll
+    for (int kk = 0; kk < j; ++kk) row += Pm[tri(j, kk)] * e[kk];
+    a += e[j] * (R(2) * row + Pm[tri(j, j)] * e[j]);
+  }
+  return a;
+}
+
+// m = max(m, a), a NaN kept: the lane's stationarity measure is then a NaN too
+template <typename R>
+__device__ __forceinline__ void ilqr_running_max(R& m, R a) {
+  if (!(a <= m)) m = a;
+}
+
+// x0, u [T][B], xs_in [T][NX][B] (NULL allowed for T == 1): the trajectory.  x0_ref [NX][B], xs_ref [T][NX][B], u_ref [T][B] or
+// NULL (zeros): the reference.  mu [B] or NULL.  PT [NX*NX][B] (lower triangle read) or NULL: diag(qf).  Outputs, each written
+// only where its pointer is given: K [T][NX][B], kff [T][B], dV [2][B], P0 [NX*NX][B] full, g0 [NX][B], hmax [B].
+template <typename R, typename M, bool PER_LANE>
+__global__ __launch_bounds__(64) void sim_ilqr_backward_kernel(
+    int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg, ExtForce<R> fe_shared, const R* fext, int n_sub, R h_last, int T,
+    const R* x0, const R* u, const R* xs_in, const R* x0_ref, const R* xs_ref, const R* u_ref, StateWeights<R, M::NX> q, R rw,
+    const R* PT, StateWeights<R, M::NX> qf, const R* mu_in, R u_limit, R* K_out, R* kff_out, R* dV_out, R* P0_out, R* g0_out,
+    R* hmax_out) {
+  constexpr int NX = M::NX, NQ = M::NQ;
+  constexpr unsigned TRIV = trivial_cols<NX, NQ>(JaZeroCols<M>::value);  // sim_jac_kernel's closed-form columns
+  constexpr int NH = tri(NX, 0);  // P's lower triangle, (j, k <= j) at tri(j, k); then g, then dV1, dV2, hmax
+  constexpr int F_G = NH, F_DV1 = NH + NX, F_DV2 = NH + NX + 1, F_HMAX = NH + NX + 2;
+  __shared__ R acc[NH + NX + 3][64];
+  const int lane = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= B) return;
+  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
+  ExtForce<R> fe = fe_shared;
+  load_ext_force<R>(fext, B, p, fe);
+  const R mu = mu_in ? mu_in[p] : R(0);
+
+  {  // P = P_T, g = P_T e_T
+    R e[NX];
+    if (xs_in) {
+#pragma unroll
+      for (int r = 0; r < NX; ++r) e[r] = xs_in[((int64_t)(T - 1) * NX + r) * B + p];
+    } else {  // T == 1: x_1 by the rollout's own sub-step
+#pragma unroll
+      for (int r = 0; r < NX; ++r) e[r] = x0[r * B + p];
+      const R uu = u[p];
+      typename M::StepCache chain;
+#pragma unroll 1
+      for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, e, chain);
+    }
+#pragma unroll
+    for (int r = 0; r < NX; ++r) e[r] -= xs_ref[((int64_t)(T - 1) * NX + r) * B + p];
+    wrap_residual<R, M>(e);
+    R Pm[NH];
+#pragma unroll
+    for (int j = 0; j < NX; ++j)
+#pragma unroll
+      for (int kk = 0; kk <= j; ++kk) {
+        Pm[tri(j, kk)] = PT ? PT[(j * NX + kk) * B + p] : (kk == j ? qf.w[j] : R(0));
+        acc[tri(j, kk)][lane] = Pm[tri(j, kk)];
+      }
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      R a = Pm[tri_sym(j, 0)] * e[0];
+#pragma unroll
+      for (int l = 1; l < NX; ++l) a += Pm[tri_sym(j, l)] * e[l];
+      acc[F_G + j][lane] = a;
+    }
+    acc[F_DV1][lane] = R(0);
+    acc[F_DV2][lane] = R(0);
+    acc[F_HMAX][lane] = R(0);
+  }
+
+#pragma unroll 1
+  for (int t = T - 1; t >= 0; --t) {
+    const R* xt = (t == 0) ? x0 : xs_in + (int64_t)(t - 1) * NX * B;
+    const R* xr = (t == 0) ? x0_ref : xs_ref + (int64_t)(t - 1) * NX * B;
+    const R uu = u[(int64_t)t * B + p];
+    if (n_sub == 0) {  // the identity plant, gamma = 0: no gain, the control's own quadratic, and P, g take the tick's state cost
+      const R du = uu - (u_ref ? u_ref[(int64_t)t * B + p] : R(0));
+      const R s = rw + mu, h = rw * du;
+      const R un = uu - du * rw / s;
+      const R kf = clampr(un, -u_limit, u_limit) - uu;
+      if (kff_out) kff_out[(int64_t)t * B + p] = kf;
+      acc[F_DV1][lane] += R(2) * kf * h;
+      acc[F_DV2][lane] += kf * kf * rw;
+      ilqr_running_max(acc[F_HMAX][lane], Math<R>::fabs(kf) * s);
+      R e[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) e[r] = xt[r * B + p] - xr[r * B + p];
+      wrap_residual<R, M>(e);
+#pragma unroll
+      for (int j = 0; j < NX; ++j) {
+        if (K_out) K_out[((int64_t)t * NX + j) * B + p] = R(0);
+        acc[tri(j, j)][lane] += q.w[j];
+        acc[F_G + j][lane] += q.w[j] * e[j];
+      }
+      continue;
+    }
+    R xs[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) xs[r] = xt[r * B + p];
+#include "sim_jac_tick.inc"  // Phi, gam, t_sum of the tick
+
+    R Pm[NH];
+#pragma unroll
+    for (int f = 0; f < NH; ++f) Pm[f] = acc[f][lane];
+    R gv[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) gv[j] = acc[F_G + j][lane];
+    const R du = uu - (u_ref ? u_ref[(int64_t)t * B + p] : R(0));
+    // ---- v = P gamma, s0 = r + gamma . v, s = s0 + mu, h = r du + gamma . g
+    R v[NX];
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      R a = Pm[tri_sym(j, 0)] * gam[0];
+#pragma unroll
+      for (int l = 1; l < NX; ++l) a += Pm[tri_sym(j, l)] * gam[l];
+      v[j] = a;
+    }
+    R s0 = rw;
+#pragma unroll
+    for (int l = 0; l < NX; ++l) s0 += gam[l] * v[l];
+    const R s = s0 + mu;
+    R h = rw * du;
+#pragma unroll
+    for (int l = 0; l < NX; ++l) h += gam[l] * gv[l];
+    // ---- the scalar box QP: the unconstrained minimiser clamped; a control on its limit takes no feedback
+    const R un = uu - h / s;
+    const R uc = clampr(un, -u_limit, u_limit);
+    const bool held = uc != un;
+    const R kf = uc - uu;
+    if (kff_out) kff_out[(int64_t)t * B + p] = kf;
+    acc[F_DV1][lane] += R(2) * kf * h;
+    acc[F_DV2][lane] += kf * kf * s0;
+    ilqr_running_max(acc[F_HMAX][lane], Math<R>::fabs(kf) * s);
+    R kt[NX];
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+      bool have = false;
+      R w = R(0);
+#pragma unroll
+      for (int l = 0; l < NX; ++l) ekf_add_term<R, NX, NQ, TRIV>(Phi, t_sum, l, c, v[l], have, w);
+      kt[c] = held ? R(0) : -(w / s);
+    }
+    if (K_out)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) K_out[((int64_t)t * NX + c) * B + p] = kt[c];
+    // ---- Acl = Phi + gamma K^T, dense
+    R Acl[NX][NX];
+#pragma unroll
+    for (int l = 0; l < NX; ++l)
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        const R g = gam[l] * kt[c];
+        Acl[l][c] = struct_zero<NX, NQ>(TRIV, l, c) ? g : phi_entry<R, M>(Phi, t_sum, l, c) + g;
+      }
+    // ---- g = q o e_t + r (du + k) K + Acl^T (g + v k)
+    {
+      R e[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) e[r] = xt[r * B + p] - xr[r * B + p];
+      wrap_residual<R, M>(e);
+      const R ru = rw * (du + kf);
+#pragma unroll
+      for (int l = 0; l < NX; ++l) gv[l] += v[l] * kf;
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        R a = Acl[0][c] * gv[0];
+#pragma unroll
+        for (int l = 1; l < NX; ++l) a += Acl[l][c] * gv[l];
+        acc[F_G + c][lane] = q.w[c] * e[c] + ru * kt[c] + a;
+      }
+    }
+    // ---- P = diag(q) + r K K^T + Acl^T P Acl, a row of Acl^T P at a time
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      R row[NX];  // row j of Acl^T P
+#pragma unroll
+      for (int c = 0; c < NX; ++c) {
+        R a = Acl[0][j] * Pm[tri_sym(0, c)];
+#pragma unroll
+        for (int l = 1; l < NX; ++l) a += Acl[l][j] * Pm[tri_sym(l, c)];
+        row[c] = a;
+      }
+#pragma unroll
+      for (int kk = 0; kk <= j; ++kk) {
+        R a = row[0] * Acl[0][kk];
+#pragma unroll
+        for (int l = 1; l < NX; ++l) a += row[l] * Acl[l][kk];
+        a += rw * kt[j] * kt[kk];
+        acc[tri(j, kk)][lane] = (kk == j) ? a + q.w[j] : a;
+      }
+    }
+  }
+
+  if (g0_out)
+#pragma unroll
+    for (int j = 0; j < NX; ++j) g0_out[j * B + p] = acc[F_G + j][lane];
+  if (dV_out) {
+    dV_out[p] = acc[F_DV1][lane];
+    dV_out[B + p] = acc[F_DV2][lane];
+  }
+  if (hmax_out) hmax_out[p] = acc[F_HMAX][lane];
+  if (P0_out) {
+    constexpr int NS = NX;
+    R* const out = P0_out;
+#include "sim_store_sym.inc"
+  }
+}
+
+// kff [T][B], K [T][NX][B], alpha [B]: each or NULL; x0_nom [NX][B] and xs_nom [T][NX][B] are read only where K is given (row
+// T-1 never).  The reference and the weights as the backward kernel's.  Outputs, each written only where its pointer is given:
+// xs_out [T][NX][B], x_final [NX][B], us_out [T][B] the controls applied, cost_out [B].
+template <typename R, typename M, bool PER_LANE>
+__global__ __launch_bounds__(64) void sim_ilqr_forward_kernel(
+    int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg, ExtForce<R> fe_shared, const R* fext, int n_sub, R h_last, int T,
+    const R* x0, const R* u_nom, const R* kff, const R* K, const R* x0_nom, const R* xs_nom, const R* alpha_in, R u_limit,
+    const R* x0_ref, const R* xs_ref, const R* u_ref, StateWeights<R, M::NX> q, R rw, const R* PT, StateWeights<R, M::NX> qf,
+    R* xs_out, R* x_final, R* us_out, R* cost_out) {
+  constexpr int NX = M::NX;
+  constexpr int NH = tri(NX, 0);
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= B) return;
+  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
+  ExtForce<R> fe = fe_shared;
+  load_ext_force<R>(fext, B, p, fe);
+  const R alpha = alpha_in ? alpha_in[p] : R(1);
+  // the terminal weights wait in vector registers for the end of the roll: as kernel arguments they would sit in scalar
+  // registers beside the folded plant constants through the whole tick loop, and the double 6-state form runs out of those
+  R qfv[NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r) {
+    qfv[r] = qf.w[r];
+    asm("" : "+v"(qfv[r]));
+  }
+  R xs[NX];
+#pragma unroll
+  for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
+  R J = R(0);
+#pragma unroll 1
+  for (int t = 0; t < T; ++t) {
+    R uu = u_nom[(int64_t)t * B + p];
+    if (kff) uu = Math<R>::fma(alpha, kff[(int64_t)t * B + p], uu);
+    if (K) {
+      const R* xn = (t == 0) ? x0_nom : xs_nom + (int64_t)(t - 1) * NX * B;
+      R d[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) d[r] = xs[r] - xn[r * B + p];
+      wrap_residual<R, M>(d);
+#pragma unroll
+      for (int r = 0; r < NX; ++r) uu = Math<R>::fma(K[((int64_t)t * NX + r) * B + p], d[r], uu);
+    }
+    uu = clampr(uu, -u_limit, u_limit);
+    if (us_out) us_out[(int64_t)t * B + p] = uu;
+    {  // the tick's cost, at its start
+      const R* xr = (t == 0) ? x0_ref : xs_ref + (int64_t)(t - 1) * NX * B;
+      R e[NX];
+#pragma unroll
+      for (int r = 0; r < NX; ++r) e[r] = xs[r] - xr[r * B + p];
+      wrap_residual<R, M>(e);
+      const R du = uu - (u_ref ? u_ref[(int64_t)t * B + p] : R(0));
+      R c = rw * du * du;
+#pragma unroll
+      for (int r = 0; r < NX; ++r) c += q.w[r] * e[r] * e[r];
+      J += c;
+    }
+    typename M::StepCache chain;
+#pragma unroll 1
+    for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
+    if (xs_out)
+#pragma unroll
+      for (int r = 0; r < NX; ++r) xs_out[((int64_t)t * NX + r) * B + p] = xs[r];
+  }
+  if (x_final)
+#pragma unroll
+    for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
+  {  // the terminal cost
+    R e[NX];
+#pragma unroll
+    for (int r = 0; r < NX; ++r) e[r] = xs[r] - xs_ref[((int64_t)(T - 1) * NX + r) * B + p];
+    wrap_residual<R, M>(e);
+    R Pm[NH];
+#pragma unroll
+    for (int j = 0; j < NX; ++j)
+#pragma unroll
+      for (int kk = 0; kk <= j; ++kk) Pm[tri(j, kk)] = PT ? PT[(j * NX + kk) * B + p] : (kk == j ? qfv[j] : R(0));
+    J += ilqr_quad_tri<R, NX>(Pm, e);
+  }
+  if (cost_out) cost_out[p] = J;
+}
+
+}  // namespace cpmpc

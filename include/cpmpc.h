@@ -818,6 +818,119 @@ typedef struct cpmpc_sim_rollout_fb {
 int cpmpc_sim_rollout_fb_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                const cpmpc_sim_rollout_fb* a, void* stream);
 
+/* ---- iterative LQR on the plant's own tick map: the backward and the forward pass of one iteration, one launch each ---- */
+/* THE COST of both calls, cpmpc_sim_lqr_batch's convention with NO factor 1/2: with e_t = wrap(x_t - xref_t) (pole angles to
+ * the nearest turn), x_0 = x0, x_t = xs[t-1], xref_0 = x0_ref, xref_t = xs_ref[t-1] and uref_t = u_ref[t] (NULL: zeros),
+ *     J = sum_{t<T} (e_t^T diag(q_host) e_t + r (u_t - uref_t)^2) + e_T^T P_T e_T
+ * Row T-1 of xs_ref IS read: it is the terminal target.  P_T is PT [NX*NX][B] (ONLY THE LOWER TRIANGLE, k <= j, IS READ), else
+ * diag(qf_host), else diag(q_host).  q_host: NX weights >= 0, NULL: ones.  r: finite and > 0.
+ *
+ * The BACKWARD PASS along the trajectory x0, u [T][B], xs [T][NX][B] -- a forward call's on the same inputs, required when
+ * T > 1; with xs == NULL and T == 1 the call rolls x_1 itself.  Reverse over the ticks, forward inside a tick, Phi_t and
+ * gamma_t of the tick at (x_t, u[t]) as cpmpc_sim_step_jac_batch's A and Bu; g is HALF the gradient of the cost-to-go:
+ *     P = P_T ;  g = P_T e_T ;  dV1 = dV2 = 0
+ *     for t = T-1 .. 0:
+ *         v   = P gamma_t ;  s0 = r + gamma_t . v ;  s = s0 + mu              mu [B] >= 0 per problem, NULL: 0
+ *         h   = r (u_t - uref_t) + gamma_t . g
+ *         k_t = clamp(u_t - h / s, +-u_limit) - u_t
+ *         K_t = (the clamp changed u_t - h / s) ? 0 : -(Phi_t^T v) / s
+ *         dV1 += 2 k_t h ;  dV2 += k_t^2 s0
+ *         Acl = Phi_t + gamma_t K_t^T
+ *         g   = q o e_t + r (u_t - uref_t + k_t) K_t + Acl^T (g + v k_t)
+ *         P   = diag(q_host) + r K_t K_t^T + Acl^T P Acl
+ * The plant has one input, so the box QP of control-limited DDP is the scalar clamp above, solved exactly, and no matrix is
+ * inverted.  SIGN CONVENTION: the improved control is u_t + alpha k_t + K_t . wrap(x - x_t), what cpmpc_sim_ilqr_forward_batch
+ * applies; alpha dV[0] + alpha^2 dV[1] is the predicted CHANGE of J (negative: a decrease) for a step alpha; x^T P0 x + 2 g0 . x
+ * is the model's cost-to-go of a deviation x at the start, up to its constant.  The P and g updates are the cost of the affine
+ * policy in the linear-quadratic model and hold for any k_t and K_t: P stays positive semidefinite under mu and under the clamp.
+ * With mu == NULL and u_limit = +infinity, K and P0 are cpmpc_sim_lqr_batch's; with the reference equal to the trajectory, kff
+ * and dV are exactly 0.
+ *     K [T][NX][B];  kff [T][B] the k_t;  dV [2][B] = dV1, dV2;  P0 [NX*NX][B] full and exactly symmetric;  g0 [NX][B];
+ *     hmax [B] = max_t |k_t| (s0 + mu), the stationarity measure: 0 where no control would move.
+ * Each output is nullable, at least one must be given, and each is bitwise the same whichever others are asked for.
+ * dt = 0 (the identity plant, gamma = 0): K = 0, k_t = clamp(u_t - (u_t - uref_t) r / (r + mu)) - u_t, g0 = P_T e_T + sum_t
+ * q o e_t, P0 = P_T + T diag(q_host).  NOT modelled: second-order terms of the dynamics (Gauss-Newton, not full DDP), cross
+ * terms or a control-rate term of the cost, feedback inside a tick.  u_limit > 0, +infinity: none; the trajectory's controls
+ * are expected inside it.  No output may overlap an input array.  A problem with non-finite data has non-finite outputs; no
+ * other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1, a
+ * wrong struct_size, r not finite and > 0, a negative or non-finite q_host or qf_host entry, u_limit not > 0, xs == NULL with
+ * T > 1, x0_ref or xs_ref == NULL, no output, and the pointer rules above -> CPMPC_ERR_INVALID_ARG, before any device is
+ * needed. */
+typedef struct cpmpc_sim_ilqr_backward {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_ilqr_backward) */
+  const void* x0;         /* [NX][B], read only: the start of the trajectory */
+  const void* u;          /* [T][B] the trajectory's controls */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* xs;         /* [T][NX][B]: a forward call's; required when T > 1 */
+  const void* x0_ref;     /* [NX][B] the target of x0 */
+  const void* xs_ref;     /* [T][NX][B] the targets of xs; row T-1 is the terminal target */
+  const void* u_ref;      /* [T][B] the controls' targets or NULL: zeros */
+  const double* q_host;   /* NX state weights >= 0, or NULL: ones */
+  double r;               /* the control weight, finite and > 0 */
+  const void* PT;         /* [NX*NX][B] terminal cost or NULL; the lower triangle is read */
+  const double* qf_host;  /* NX terminal weights >= 0 used where PT is NULL, or NULL: q_host's */
+  const void* mu;         /* [B] regularisation >= 0 added to s, or NULL: none */
+  double u_limit;         /* > 0; +infinity: no limit */
+  void* K;                /* [T][NX][B] or NULL */
+  void* kff;              /* [T][B] or NULL */
+  void* dV;               /* [2][B] or NULL */
+  void* P0;               /* [NX*NX][B] or NULL */
+  void* g0;               /* [NX][B] or NULL */
+  void* hmax;             /* [B] or NULL */
+} cpmpc_sim_ilqr_backward;
+int cpmpc_sim_ilqr_backward_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                  const cpmpc_sim_ilqr_backward* a, void* stream);
+
+/* The FORWARD PASS: cpmpc_sim_rollout_fb_batch's loop with a per-problem step on the feedforward term and the cost J above
+ * summed on the device,
+ *     d   = wrap(x_t - x_nom_t)                       x_nom_0 = x0_nom, x_nom_t = xs_nom[t-1]; row T-1 of xs_nom is never read
+ *     u_t = clamp(u_nom[t] + alpha kff[t] + K[t] . d, +-u_limit)
+ *     x_{t+1} = Step(x_t, u_t, dt)
+ *     cost = J of (x0, the states passed, the controls applied) against x0_ref, xs_ref, u_ref
+ * kff [T][B], K [T][NX][B]: cpmpc_sim_ilqr_backward_batch's, each or NULL (that term is absent); K needs x0_nom, and xs_nom
+ * when T > 1.  alpha [B]: a step per problem, a DEVICE array, NULL: 1.  With kff == K == NULL this is the plain clamped rollout
+ * with its cost -- how a loop gets its first trajectory -- and with u_limit = +infinity its xs are cpmpc_sim_rollout_batch's
+ * bit for bit.  With x0 == x0_nom, the nominal's parameters, alpha = 0 and finite kff, K, the call reproduces the nominal xs
+ * and us (a forward call's own) and their cost bit for bit.
+ *     xs [T][NX][B], x_final [NX][B], us [T][B] the controls applied, cost [B];
+ * each is nullable, at least one must be given, and each is bitwise the same whichever others are asked for.  dt = 0: the
+ * state stays, us and cost as written.  There is NO feedback inside a tick.  No output may overlap an input array.  A problem
+ * with non-finite data has non-finite outputs; no other problem is affected.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  dt < 0 or non-finite, T < 1, a
+ * wrong struct_size, r not finite and > 0, a negative or non-finite q_host or qf_host entry, u_limit not > 0, x0_ref or xs_ref
+ * == NULL, K without x0_nom (or without xs_nom when T > 1), no output, and the pointer rules above -> CPMPC_ERR_INVALID_ARG,
+ * before any device is needed. */
+typedef struct cpmpc_sim_ilqr_forward {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_ilqr_forward) */
+  const void* x0;         /* [NX][B], read only */
+  const void* u_nom;      /* [T][B] the nominal controls */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* kff;        /* [T][B] feedforward terms or NULL */
+  const void* K;          /* [T][NX][B] gains or NULL: no feedback */
+  const void* x0_nom;     /* [NX][B] the nominal start; required where K is given */
+  const void* xs_nom;     /* [T][NX][B] the nominal checkpoints; required where K is given and T > 1 */
+  const void* alpha;      /* [B] the step on kff per problem, or NULL: 1 */
+  double u_limit;         /* > 0; +infinity: no clamp */
+  const void* x0_ref;     /* [NX][B] the target of x0 */
+  const void* xs_ref;     /* [T][NX][B] the targets of xs; row T-1 is the terminal target */
+  const void* u_ref;      /* [T][B] the controls' targets or NULL: zeros */
+  const double* q_host;   /* NX state weights >= 0, or NULL: ones */
+  double r;               /* the control weight, finite and > 0 */
+  const void* PT;         /* [NX*NX][B] terminal cost or NULL; the lower triangle is read */
+  const double* qf_host;  /* NX terminal weights >= 0 used where PT is NULL, or NULL: q_host's */
+  void* xs;               /* [T][NX][B] or NULL */
+  void* x_final;          /* [NX][B] or NULL */
+  void* us;               /* [T][B] or NULL */
+  void* cost;             /* [B] or NULL */
+} cpmpc_sim_ilqr_forward;
+int cpmpc_sim_ilqr_forward_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                 const cpmpc_sim_ilqr_forward* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
