@@ -1177,6 +1177,14 @@ extern "C" int cpmpc_sim_rts_batch(int model, int dtype, int64_t B, const double
 }
 
 // ---- tracking a plant trajectory: its LQR gains and the plant under them (sim_track_kernels.hpp) -----------------------
+// The weights of the tracking cost, which sim_lqr and the two iLQR passes check alike: r, then q_host, then qf_host
+static int check_track_weights(double r, const double* q_host, const double* qf_host, size_t nx) {
+  if (!(r > 0.0) || !std::isfinite(r)) return fail(CPMPC_ERR_INVALID_ARG, "r must be finite and > 0");
+  int rc = check_host_weights("q_host", q_host, nx);
+  if (!rc) rc = check_host_weights("qf_host", qf_host, nx);
+  return rc;
+}
+
 static int check_sim_lqr_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                               const cpmpc_sim_lqr* a) {
   if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_lqr)");
@@ -1185,10 +1193,8 @@ static int check_sim_lqr_args(int model, int dtype, int64_t B, const double* dyn
   if (rc) return rc;
   if (!a->K && !a->P0) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
   if (T > 1 && !a->xs) return fail(CPMPC_ERR_INVALID_ARG, "xs (a forward call's checkpoints) is required when T > 1");
-  if (!(a->r > 0.0) || !std::isfinite(a->r)) return fail(CPMPC_ERR_INVALID_ARG, "r must be finite and > 0");
   const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
-  rc = check_host_weights("q_host", a->q_host, nx);
-  if (!rc) rc = check_host_weights("qf_host", a->qf_host, nx);
+  rc = check_track_weights(a->r, a->q_host, a->qf_host, nx);
   if (rc) return rc;
   const ArraySpan outs[2] = {{a->K, nt * nx, "K"}, {a->P0, nx * nx, "P0"}};
   const ArraySpan ins[6] = {{a->x0, nx, "x0"},     {a->u, nt, "u"},        {a->fext, 4, "fext"},
@@ -1205,30 +1211,44 @@ extern "C" int cpmpc_sim_lqr_batch(int model, int dtype, int64_t B, const double
   });
 }
 
-static int check_sim_rollout_fb_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
-                                     const cpmpc_sim_rollout_fb* a) {
-  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_rollout_fb)");
-  int rc = check_struct_size("cpmpc_sim_rollout_fb", a->struct_size, sizeof(cpmpc_sim_rollout_fb));
+// What the two calls that roll the plant under a feedback law (the fb rollout, the iLQR's forward pass) check first: the
+// struct `what`, u_nom by its own name, then the rollout's rules
+template <typename Args>
+static int check_fb_rollout_common(const char* what, const Args* a, const double* dyn_shared_host, double dt, int T, int model,
+                                   int dtype, int64_t B) {
+  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (%s)", what);
+  int rc = check_struct_size(what, a->struct_size, sizeof(Args));
   if (rc) return rc;
   if (!a->u_nom) return fail(CPMPC_ERR_INVALID_ARG, "null argument (u_nom)");
-  rc = check_rollout_common("cpmpc_sim_rollout_fb", a->struct_size, sizeof(cpmpc_sim_rollout_fb), a->x0, a->u_nom,
-                            dyn_shared_host, a->dyn, dt, T, model, dtype, B);
-  if (rc) return rc;
-  if (!a->xs && !a->x_final && !a->us) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
-  if (!(a->u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no clamp)");
+  return check_rollout_common(what, a->struct_size, sizeof(Args), a->x0, a->u_nom, dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+}
+
+// ... and last before the overlaps: K needs the nominal trajectory it is a gain about.  `law`: the spans of K and of that
+// trajectory, which is read only where K is given
+template <typename Args>
+static int check_feedback_law(const Args* a, int T, size_t nx, size_t nt, ArraySpan (&law)[3]) {
   if (a->K && !a->x0_nom) return fail(CPMPC_ERR_INVALID_ARG, "K is given without x0_nom");
   if (a->K && T > 1 && !a->xs_nom)
     return fail(CPMPC_ERR_INVALID_ARG, "K is given without xs_nom (the nominal checkpoints), required when T > 1");
+  law[0] = {a->K, nt * nx, "K"};
+  law[1] = {a->K ? a->x0_nom : nullptr, nx, "x0_nom"};
+  law[2] = {a->K ? a->xs_nom : nullptr, nt * nx, "xs_nom"};
+  return CPMPC_OK;
+}
+
+static int check_sim_rollout_fb_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                     const cpmpc_sim_rollout_fb* a) {
+  int rc = check_fb_rollout_common("cpmpc_sim_rollout_fb", a, dyn_shared_host, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->xs && !a->x_final && !a->us) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  if (!(a->u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no clamp)");
   const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  ArraySpan law[3];
+  rc = check_feedback_law(a, T, nx, nt, law);
+  if (rc) return rc;
   const ArraySpan outs[3] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}, {a->us, nt, "us"}};
-  // the nominal trajectory is read only where K is given
-  const ArraySpan ins[7] = {{a->x0, nx, "x0"},
-                            {a->u_nom, nt, "u_nom"},
-                            {a->fext, 4, "fext"},
-                            {a->dyn, np, "dyn"},
-                            {a->K, nt * nx, "K"},
-                            {a->K ? a->x0_nom : nullptr, nx, "x0_nom"},
-                            {a->K ? a->xs_nom : nullptr, nt * nx, "xs_nom"}};
+  const ArraySpan ins[7] = {{a->x0, nx, "x0"}, {a->u_nom, nt, "u_nom"}, {a->fext, 4, "fext"}, {a->dyn, np, "dyn"},
+                            law[0],            law[1],                  law[2]};
   return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }
 
@@ -1245,9 +1265,7 @@ extern "C" int cpmpc_sim_rollout_fb_batch(int model, int dtype, int64_t B, const
 // what the two calls share beyond check_rollout_common: the cost's weights, the limit and the reference
 template <typename Args>
 static int check_sim_ilqr_cost(const Args* a, size_t nx) {
-  if (!(a->r > 0.0) || !std::isfinite(a->r)) return fail(CPMPC_ERR_INVALID_ARG, "r must be finite and > 0");
-  int rc = check_host_weights("q_host", a->q_host, nx);
-  if (!rc) rc = check_host_weights("qf_host", a->qf_host, nx);
+  int rc = check_track_weights(a->r, a->q_host, a->qf_host, nx);
   if (rc) return rc;
   if (!(a->u_limit > 0.0)) return fail(CPMPC_ERR_INVALID_ARG, "u_limit must be > 0 (infinity: no limit)");
   if (!a->x0_ref || !a->xs_ref)
@@ -1288,34 +1306,20 @@ extern "C" int cpmpc_sim_ilqr_backward_batch(int model, int dtype, int64_t B, co
 
 static int check_sim_ilqr_forward_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                        const cpmpc_sim_ilqr_forward* a) {
-  if (!a) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cpmpc_sim_ilqr_forward)");
-  int rc = check_struct_size("cpmpc_sim_ilqr_forward", a->struct_size, sizeof(cpmpc_sim_ilqr_forward));
-  if (rc) return rc;
-  if (!a->u_nom) return fail(CPMPC_ERR_INVALID_ARG, "null argument (u_nom)");
-  rc = check_rollout_common("cpmpc_sim_ilqr_forward", a->struct_size, sizeof(cpmpc_sim_ilqr_forward), a->x0, a->u_nom,
-                            dyn_shared_host, a->dyn, dt, T, model, dtype, B);
+  int rc = check_fb_rollout_common("cpmpc_sim_ilqr_forward", a, dyn_shared_host, dt, T, model, dtype, B);
   if (rc) return rc;
   if (!a->xs && !a->x_final && !a->us && !a->cost) return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
   const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
   rc = check_sim_ilqr_cost(a, nx);
   if (rc) return rc;
-  if (a->K && !a->x0_nom) return fail(CPMPC_ERR_INVALID_ARG, "K is given without x0_nom");
-  if (a->K && T > 1 && !a->xs_nom)
-    return fail(CPMPC_ERR_INVALID_ARG, "K is given without xs_nom (the nominal checkpoints), required when T > 1");
+  ArraySpan law[3];
+  rc = check_feedback_law(a, T, nx, nt, law);
+  if (rc) return rc;
   const ArraySpan outs[4] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}, {a->us, nt, "us"}, {a->cost, 1, "cost"}};
-  // the nominal trajectory is read only where K is given
-  const ArraySpan ins[13] = {{a->x0, nx, "x0"},
-                             {a->u_nom, nt, "u_nom"},
-                             {a->fext, 4, "fext"},
-                             {a->dyn, np, "dyn"},
-                             {a->kff, nt, "kff"},
-                             {a->K, nt * nx, "K"},
-                             {a->K ? a->x0_nom : nullptr, nx, "x0_nom"},
-                             {a->K ? a->xs_nom : nullptr, nt * nx, "xs_nom"},
-                             {a->alpha, 1, "alpha"},
-                             {a->x0_ref, nx, "x0_ref"},
-                             {a->xs_ref, nt * nx, "xs_ref"},
-                             {a->u_ref, nt, "u_ref"},
+  const ArraySpan ins[13] = {{a->x0, nx, "x0"},         {a->u_nom, nt, "u_nom"},         {a->fext, 4, "fext"},
+                             {a->dyn, np, "dyn"},       {a->kff, nt, "kff"},             law[0],
+                             law[1],                    law[2],                          {a->alpha, 1, "alpha"},
+                             {a->x0_ref, nx, "x0_ref"}, {a->xs_ref, nt * nx, "xs_ref"},  {a->u_ref, nt, "u_ref"},
                              {a->PT, nx * nx, "PT"}};
   return check_no_overlap(outs, ins, row_bytes(dtype, B));
 }

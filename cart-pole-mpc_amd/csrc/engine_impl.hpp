@@ -651,18 +651,25 @@ static void sim_rts_impl(int64_t B, const double* dyn_shared_host, int n_sub, do
 }
 
 // ---- tracking a plant trajectory: its LQR gains, and the plant under them, one launch each (sim_track_kernels.hpp) --------
-// the terminal diagonal where PT is NULL: qf_host, else q_host, else ones
+// The weights of the tracking cost as sim_lqr and the two iLQR passes take them: q, NULL: ones; and qf, the terminal diagonal
+// where PT is NULL: qf_host, else q_host, else ones
+template <typename R, int NX>
+struct TrackWeights {
+  StateWeights<R, NX> q, qf;
+  TrackWeights(const double* q_host, const double* qf_host)
+      : q(state_weights<R, NX>(q_host, 1.0)), qf(state_weights<R, NX>(qf_host ? qf_host : q_host, 1.0)) {}
+};
+
 template <typename R, typename M>
 static void sim_lqr_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T, const cpmpc_sim_lqr* a,
                          hipStream_t stream) {
-  const StateWeights<R, M::NX> q = state_weights<R, M::NX>(a->q_host, 1.0),
-                               qf = state_weights<R, M::NX>(a->qf_host ? a->qf_host : a->q_host, 1.0);
+  const TrackWeights<R, M::NX> w(a->q_host, a->qf_host);
   with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
     constexpr bool PL = decltype(per_lane)::value;
     hipLaunchKernelGGL((sim_lqr_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
                        plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
-                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u, (const R*)a->xs, q, (R)a->r, (const R*)a->PT, qf,
-                       (R*)a->K, (R*)a->P0);
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u, (const R*)a->xs, w.q, (R)a->r, (const R*)a->PT,
+                       w.qf, (R*)a->K, (R*)a->P0);
   });
 }
 
@@ -679,18 +686,16 @@ static void sim_rollout_fb_impl(int64_t B, const double* dyn_shared_host, int n_
 }
 
 // ---- one iLQR iteration on the plant's tick map: the backward and the forward pass, one launch each (sim_ilqr_kernels.hpp) ----
-// the terminal diagonal where PT is NULL: qf_host, else q_host, else ones -- sim_lqr_impl's rule
 template <typename R, typename M>
 static void sim_ilqr_backward_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                                    const cpmpc_sim_ilqr_backward* a, hipStream_t stream) {
-  const StateWeights<R, M::NX> q = state_weights<R, M::NX>(a->q_host, 1.0),
-                               qf = state_weights<R, M::NX>(a->qf_host ? a->qf_host : a->q_host, 1.0);
+  const TrackWeights<R, M::NX> w(a->q_host, a->qf_host);
   with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
     constexpr bool PL = decltype(per_lane)::value;
     hipLaunchKernelGGL((sim_ilqr_backward_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
                        plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
                        n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u, (const R*)a->xs, (const R*)a->x0_ref,
-                       (const R*)a->xs_ref, (const R*)a->u_ref, q, (R)a->r, (const R*)a->PT, qf, (const R*)a->mu,
+                       (const R*)a->xs_ref, (const R*)a->u_ref, w.q, (R)a->r, (const R*)a->PT, w.qf, (const R*)a->mu,
                        (R)a->u_limit, (R*)a->K, (R*)a->kff, (R*)a->dV, (R*)a->P0, (R*)a->g0, (R*)a->hmax);
   });
 }
@@ -698,15 +703,14 @@ static void sim_ilqr_backward_impl(int64_t B, const double* dyn_shared_host, int
 template <typename R, typename M>
 static void sim_ilqr_forward_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                                   const cpmpc_sim_ilqr_forward* a, hipStream_t stream) {
-  const StateWeights<R, M::NX> q = state_weights<R, M::NX>(a->q_host, 1.0),
-                               qf = state_weights<R, M::NX>(a->qf_host ? a->qf_host : a->q_host, 1.0);
+  const TrackWeights<R, M::NX> w(a->q_host, a->qf_host);
   with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
     constexpr bool PL = decltype(per_lane)::value;
     hipLaunchKernelGGL((sim_ilqr_forward_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
                        plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
                        n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u_nom, (const R*)a->kff, (const R*)a->K,
                        (const R*)a->x0_nom, (const R*)a->xs_nom, (const R*)a->alpha, (R)a->u_limit, (const R*)a->x0_ref,
-                       (const R*)a->xs_ref, (const R*)a->u_ref, q, (R)a->r, (const R*)a->PT, qf, (R*)a->xs, (R*)a->x_final,
+                       (const R*)a->xs_ref, (const R*)a->u_ref, w.q, (R)a->r, (const R*)a->PT, w.qf, (R*)a->xs, (R*)a->x_final,
                        (R*)a->us, (R*)a->cost);
   });
 }

@@ -22,7 +22,9 @@
 //     P0 = P ;  g0 = g
 // alpha dV1 + alpha^2 dV2 is the predicted change of J for a step alpha.  The P and g updates are the cost of the affine policy
 // du = k + K_t dx in the linear-quadratic model and hold for ANY k and K_t, so P stays a sum of positive semidefinite terms
-// under mu and under the clamp.  With mu NULL and no limit the P and K arithmetic is sim_lqr_kernel's, statement for statement.
+// under mu and under the clamp.  The P and K arithmetic is sim_lqr_kernel's own text, the parts of
+// sim_riccati.inc; what is written here is the iLQR's alone: g, h, the scalar box QP, the three sums, the reference's loads
+// and the zero gain of a held control.  So with mu NULL and no limit K and P0 are sim_lqr's bit for bit.
 // x_T is xs[T-1]; where xs is NULL (allowed for T == 1) it is rolled from x0 by plant_sub_step, the rollout's own function.
 // P's triangle, g, and the three running sums live in lane-private LDS, acc[field][threadIdx.x], while the sub-step loop runs:
 // what is live there is sim_jac_kernel's set; x_t is loaded again after the tick for e_t.  Everything is computed whichever
@@ -30,9 +32,10 @@
 // k = clamp(u - (u - uref) r / (r + mu)) - u, g += q o e_t, P += diag(q), written as that.  Not modelled: second-order terms of
 // the dynamics (this is Gauss-Newton), cross terms of the cost, feedback inside a tick.
 //
-// sim_ilqr_forward_kernel: sim_rollout_fb_kernel's loop with a per-lane step on the feedforward term and the cost summed,
+// sim_ilqr_forward_kernel: the one body of the forward kernels, sim_roll_ticks.inc, with its law and
+// its cost both compiled in -- sim_rollout_fb_kernel's loop with a per-lane step on the feedforward term and the cost summed,
 //     u_t = clamp(u_nom[t] + alpha[p] kff[t] + K[t] . wrap_residual(x_t - x_nom_t), +-u_limit)
-//     x_{t+1} = Step(x_t, u_t, dt)                                            plant_sub_step, unchanged
+//     x_{t+1} = Step(x_t, u_t, dt)                                            plant_sub_step
 //     cost = J of (x0, xs, us) against the reference
 // kff and K are each nullable; with both NULL and u_limit = +inf it is sim_rollout_kernel bit for bit, with its cost.  alpha
 // NULL means 1.  From the nominal start with alpha = 0 the deviation is exactly 0 at every tick and the nominal controls (a
@@ -41,20 +44,6 @@
 #include "sim_track_kernels.hpp"
 
 namespace cpmpc {
-
-// e^T P e with P's lower triangle in Pm (tri), or sum qf e^2 where there is no tensor
-template <typename R, int NX>
-__device__ __forceinline__ R ilqr_quad_tri(const R (&Pm)[tri(NX, 0)], const R (&e)[NX]) {
-  R a = R(0);
-#pragma unroll
-  for (int j = 0; j < NX; ++j) {
-    R row = R(0);
-#pragma unroll
-    for (int kk = 0; kk < j; ++kk) row += Pm[tri(j, kk)] * e[kk];
-    a += e[j] * (R(2) * row + Pm[tri(j, j)] * e[j]);
-  }
-  return a;
-}
 
 // m = max(m, a), a NaN kept: the lane's stationarity measure is then a NaN too
 template <typename R>
@@ -159,17 +148,8 @@ __global__ __launch_bounds__(64) void sim_ilqr_backward_kernel(
     for (int j = 0; j < NX; ++j) gv[j] = acc[F_G + j][lane];
     const R du = uu - (u_ref ? u_ref[(int64_t)t * B + p] : R(0));
     // ---- v = P gamma, s0 = r + gamma . v, s = s0 + mu, h = r du + gamma . g
-    R v[NX];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      R a = Pm[tri_sym(j, 0)] * gam[0];
-#pragma unroll
-      for (int l = 1; l < NX; ++l) a += Pm[tri_sym(j, l)] * gam[l];
-      v[j] = a;
-    }
-    R s0 = rw;
-#pragma unroll
-    for (int l = 0; l < NX; ++l) s0 += gam[l] * v[l];
+#define CPMPC_RICCATI_V_S0
+#include "sim_riccati.inc"
     const R s = s0 + mu;
     R h = rw * du;
 #pragma unroll
@@ -183,27 +163,10 @@ __global__ __launch_bounds__(64) void sim_ilqr_backward_kernel(
     acc[F_DV1][lane] += R(2) * kf * h;
     acc[F_DV2][lane] += kf * kf * s0;
     ilqr_running_max(acc[F_HMAX][lane], Math<R>::fabs(kf) * s);
-    R kt[NX];
-#pragma unroll
-    for (int c = 0; c < NX; ++c) {
-      bool have = false;
-      R w = R(0);
-#pragma unroll
-      for (int l = 0; l < NX; ++l) ekf_add_term<R, NX, NQ, TRIV>(Phi, t_sum, l, c, v[l], have, w);
-      kt[c] = held ? R(0) : -(w / s);
-    }
-    if (K_out)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) K_out[((int64_t)t * NX + c) * B + p] = kt[c];
-    // ---- Acl = Phi + gamma K^T, dense
-    R Acl[NX][NX];
-#pragma unroll
-    for (int l = 0; l < NX; ++l)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        const R g = gam[l] * kt[c];
-        Acl[l][c] = struct_zero<NX, NQ>(TRIV, l, c) ? g : phi_entry<R, M>(Phi, t_sum, l, c) + g;
-      }
+#define CPMPC_RICCATI_GAIN(k) (held ? R(0) : (k))
+#define CPMPC_RICCATI_GAIN_ACL
+#include "sim_riccati.inc"
+#undef CPMPC_RICCATI_GAIN
     // ---- g = q o e_t + r (du + k) K + Acl^T (g + v k)
     {
       R e[NX];
@@ -221,26 +184,8 @@ __global__ __launch_bounds__(64) void sim_ilqr_backward_kernel(
         acc[F_G + c][lane] = q.w[c] * e[c] + ru * kt[c] + a;
       }
     }
-    // ---- P = diag(q) + r K K^T + Acl^T P Acl, a row of Acl^T P at a time
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      R row[NX];  // row j of Acl^T P
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R a = Acl[0][j] * Pm[tri_sym(0, c)];
-#pragma unroll
-        for (int l = 1; l < NX; ++l) a += Acl[l][j] * Pm[tri_sym(l, c)];
-        row[c] = a;
-      }
-#pragma unroll
-      for (int kk = 0; kk <= j; ++kk) {
-        R a = row[0] * Acl[0][kk];
-#pragma unroll
-        for (int l = 1; l < NX; ++l) a += row[l] * Acl[l][kk];
-        a += rw * kt[j] * kt[kk];
-        acc[tri(j, kk)][lane] = (kk == j) ? a + q.w[j] : a;
-      }
-    }
+#define CPMPC_RICCATI_UPDATE
+#include "sim_riccati.inc"
   }
 
   if (g0_out)
@@ -258,6 +203,20 @@ __global__ __launch_bounds__(64) void sim_ilqr_backward_kernel(
   }
 }
 
+// e^T P e with P's lower triangle in Pm (tri), or sum qf e^2 where there is no tensor: the terminal cost of sim_roll_ticks.inc
+template <typename R, int NX>
+__device__ __forceinline__ R ilqr_quad_tri(const R (&Pm)[tri(NX, 0)], const R (&e)[NX]) {
+  R a = R(0);
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    R row = R(0);
+#pragma unroll
+    for (int kk = 0; kk < j; ++kk) row += Pm[tri(j, kk)] * e[kk];
+    a += e[j] * (R(2) * row + Pm[tri(j, j)] * e[j]);
+  }
+  return a;
+}
+
 // kff [T][B], K [T][NX][B], alpha [B]: each or NULL; x0_nom [NX][B] and xs_nom [T][NX][B] are read only where K is given (row
 // T-1 never).  The reference and the weights as the backward kernel's.  Outputs, each written only where its pointer is given:
 // xs_out [T][NX][B], x_final [NX][B], us_out [T][B] the controls applied, cost_out [B].
@@ -267,76 +226,9 @@ __global__ __launch_bounds__(64) void sim_ilqr_forward_kernel(
     const R* x0, const R* u_nom, const R* kff, const R* K, const R* x0_nom, const R* xs_nom, const R* alpha_in, R u_limit,
     const R* x0_ref, const R* xs_ref, const R* u_ref, StateWeights<R, M::NX> q, R rw, const R* PT, StateWeights<R, M::NX> qf,
     R* xs_out, R* x_final, R* us_out, R* cost_out) {
-  constexpr int NX = M::NX;
-  constexpr int NH = tri(NX, 0);
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= B) return;
-  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
-  ExtForce<R> fe = fe_shared;
-  load_ext_force<R>(fext, B, p, fe);
-  const R alpha = alpha_in ? alpha_in[p] : R(1);
-  // the terminal weights wait in vector registers for the end of the roll: as kernel arguments they would sit in scalar
-  // registers beside the folded plant constants through the whole tick loop, and the double 6-state form runs out of those
-  R qfv[NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r) {
-    qfv[r] = qf.w[r];
-    asm("" : "+v"(qfv[r]));
-  }
-  R xs[NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
-  R J = R(0);
-#pragma unroll 1
-  for (int t = 0; t < T; ++t) {
-    R uu = u_nom[(int64_t)t * B + p];
-    if (kff) uu = Math<R>::fma(alpha, kff[(int64_t)t * B + p], uu);
-    if (K) {
-      const R* xn = (t == 0) ? x0_nom : xs_nom + (int64_t)(t - 1) * NX * B;
-      R d[NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) d[r] = xs[r] - xn[r * B + p];
-      wrap_residual<R, M>(d);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) uu = Math<R>::fma(K[((int64_t)t * NX + r) * B + p], d[r], uu);
-    }
-    uu = clampr(uu, -u_limit, u_limit);
-    if (us_out) us_out[(int64_t)t * B + p] = uu;
-    {  // the tick's cost, at its start
-      const R* xr = (t == 0) ? x0_ref : xs_ref + (int64_t)(t - 1) * NX * B;
-      R e[NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) e[r] = xs[r] - xr[r * B + p];
-      wrap_residual<R, M>(e);
-      const R du = uu - (u_ref ? u_ref[(int64_t)t * B + p] : R(0));
-      R c = rw * du * du;
-#pragma unroll
-      for (int r = 0; r < NX; ++r) c += q.w[r] * e[r] * e[r];
-      J += c;
-    }
-    typename M::StepCache chain;
-#pragma unroll 1
-    for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
-    if (xs_out)
-#pragma unroll
-      for (int r = 0; r < NX; ++r) xs_out[((int64_t)t * NX + r) * B + p] = xs[r];
-  }
-  if (x_final)
-#pragma unroll
-    for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
-  {  // the terminal cost
-    R e[NX];
-#pragma unroll
-    for (int r = 0; r < NX; ++r) e[r] = xs[r] - xs_ref[((int64_t)(T - 1) * NX + r) * B + p];
-    wrap_residual<R, M>(e);
-    R Pm[NH];
-#pragma unroll
-    for (int j = 0; j < NX; ++j)
-#pragma unroll
-      for (int kk = 0; kk <= j; ++kk) Pm[tri(j, kk)] = PT ? PT[(j * NX + kk) * B + p] : (kk == j ? qfv[j] : R(0));
-    J += ilqr_quad_tri<R, NX>(Pm, e);
-  }
-  if (cost_out) cost_out[p] = J;
+#define CPMPC_ROLL_LAW 1
+#define CPMPC_ROLL_COST 1
+#include "sim_roll_ticks.inc"
 }
 
 }  // namespace cpmpc

@@ -6,7 +6,9 @@
 //
 // sim_rollout_kernel: a tick is n_sub calls of plant_sub_step (plant_kernels.hpp), the function sim_kernel's loop calls; after
 // tick t it stores x_{t+1} to xs [T][NX][B] (field t*NX + r) and after the last one to x_final [NX][B], each where its pointer
-// is given (a wave-uniform choice).
+// is given (a wave-uniform choice).  Its body is sim_roll_ticks.inc, written once for this kernel, sim_rollout_fb_kernel
+// (sim_track_kernels.hpp: the loop under a feedback law) and sim_ilqr_forward_kernel (sim_ilqr_kernels.hpp: the law and the
+// cost); the law and the cost are compile-time parts of that text, and this kernel compiles neither.
 //
 // sim_rollout_vjp_kernel: REVERSE over the ticks, FORWARD inside a tick.  With the cotangents gbar [T][NX][B] on every
 // x_{t+1} and / or gbar_final [NX][B] on x_T,
@@ -33,29 +35,10 @@ namespace cpmpc {
 template <typename R, typename M, bool PER_LANE>
 __global__ __launch_bounds__(64) void sim_rollout_kernel(int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg,
                                                           ExtForce<R> fe_shared, const R* fext, int n_sub, R h_last, int T,
-                                                          const R* x0, const R* u, R* xs_out, R* x_final) {
-  constexpr int NX = M::NX;
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= B) return;
-  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
-  ExtForce<R> fe = fe_shared;
-  load_ext_force<R>(fext, B, p, fe);
-  R xs[NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
-#pragma unroll 1
-  for (int t = 0; t < T; ++t) {
-    const R uu = u[(int64_t)t * B + p];
-    typename M::StepCache chain;
-#pragma unroll 1
-    for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
-    if (xs_out)
-#pragma unroll
-      for (int r = 0; r < NX; ++r) xs_out[((int64_t)t * NX + r) * B + p] = xs[r];
-  }
-  if (x_final)
-#pragma unroll
-    for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
+                                                          const R* x0, const R* u_nom, R* xs_out, R* x_final) {
+#define CPMPC_ROLL_LAW 0
+#define CPMPC_ROLL_COST 0
+#include "sim_roll_ticks.inc"
 }
 
 // PER_LANE: the parameters are dyn [NP][B], read per lane (sim_param_load.inc), and the constants are M::make<R> of them in

@@ -22,13 +22,15 @@
 // same whatever else is asked for, and a window of T1 + T2 ticks is bitwise the T2-tick tail's P0 fed as PT into the T1-tick
 // head: P0 leaves by sim_store_sym.inc from the triangle PT's is read into.  n_sub == 0 is the identity plant with gamma = 0:
 // k_t = 0 and P += diag(q), written as that.  Not modelled: the clamp of the control, feedback inside a tick, cross terms of
-// the cost.
+// the cost.  The step's arithmetic is written once, as the parts of sim_riccati.inc, and sim_ilqr_backward_kernel
+// (sim_ilqr_kernels.hpp) is made of the same parts: with no regularisation and no limit the iLQR's K and P0 are this kernel's bit for bit because they
+// are this kernel's text, and a change to the step (a gT beside PT) is made in one place.
 //
-// sim_rollout_fb_kernel: sim_rollout_kernel's loop with the tick's control formed at the tick's start and held over its
-// sub-steps,
+// sim_rollout_fb_kernel: sim_rollout_kernel's body, sim_roll_ticks.inc, with its law compiled in: the
+// tick's control is formed at the tick's start and held over its sub-steps,
 //     d   = wrap_residual(x_t - x_nom_t)                  x_nom_0 = x0_nom, x_nom_t = xs_nom[t-1]; row T-1 is never loaded
 //     u_t = clamp(u_nom[t] + K[t] . d, +-u_limit)         -> us[t]
-//     x_{t+1} = Step(x_t, u_t, dt)                        plant_sub_step, the function sim_rollout_kernel's loop calls
+//     x_{t+1} = Step(x_t, u_t, dt)                        plant_sub_step, in the one loop all three forward kernels run
 // With K == NULL the nominal trajectory is not read and u_t = clamp(u_nom[t]); with u_limit = +inf the clamp returns its
 // argument, so that call is sim_rollout_kernel bit for bit.  With x0 == x0_nom and the nominal trajectory's own parameters d is
 // exactly 0 at every tick, K[t] . 0 adds nothing to a non-zero u_nom[t], and the call reproduces the nominal rollout bit for bit.
@@ -56,7 +58,6 @@ __global__ __launch_bounds__(64) void sim_lqr_kernel(int64_t B, typename PlantCo
   const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
   ExtForce<R> fe = fe_shared;
   load_ext_force<R>(fext, B, p, fe);
-
 #pragma unroll
   for (int j = 0; j < NX; ++j)
 #pragma unroll
@@ -83,59 +84,15 @@ __global__ __launch_bounds__(64) void sim_lqr_kernel(int64_t B, typename PlantCo
     R Pm[NH];
 #pragma unroll
     for (int f = 0; f < NH; ++f) Pm[f] = acc[f][lane];
-    // ---- v = P gamma, s = r + gamma . v, k = -(Phi^T v) / s
-    R v[NX];
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      R a = Pm[tri_sym(j, 0)] * gam[0];
-#pragma unroll
-      for (int l = 1; l < NX; ++l) a += Pm[tri_sym(j, l)] * gam[l];
-      v[j] = a;
-    }
-    R s = rw;
-#pragma unroll
-    for (int l = 0; l < NX; ++l) s += gam[l] * v[l];
-    R kt[NX];
-#pragma unroll
-    for (int c = 0; c < NX; ++c) {
-      bool have = false;
-      R w = R(0);
-#pragma unroll
-      for (int l = 0; l < NX; ++l) ekf_add_term<R, NX, NQ, TRIV>(Phi, t_sum, l, c, v[l], have, w);
-      kt[c] = -(w / s);
-    }
-    if (K_out)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) K_out[((int64_t)t * NX + c) * B + p] = kt[c];
-    // ---- Acl = Phi + gamma k^T, dense
-    R Acl[NX][NX];
-#pragma unroll
-    for (int l = 0; l < NX; ++l)
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        const R g = gam[l] * kt[c];
-        Acl[l][c] = struct_zero<NX, NQ>(TRIV, l, c) ? g : phi_entry<R, M>(Phi, t_sum, l, c) + g;
-      }
-    // ---- P = diag(q) + r k k^T + Acl^T P Acl, a row of Acl^T P at a time
-#pragma unroll
-    for (int j = 0; j < NX; ++j) {
-      R row[NX];  // row j of Acl^T P
-#pragma unroll
-      for (int c = 0; c < NX; ++c) {
-        R a = Acl[0][j] * Pm[tri_sym(0, c)];
-#pragma unroll
-        for (int l = 1; l < NX; ++l) a += Acl[l][j] * Pm[tri_sym(l, c)];
-        row[c] = a;
-      }
-#pragma unroll
-      for (int kk = 0; kk <= j; ++kk) {
-        R a = row[0] * Acl[0][kk];
-#pragma unroll
-        for (int l = 1; l < NX; ++l) a += row[l] * Acl[l][kk];
-        a += rw * kt[j] * kt[kk];
-        acc[tri(j, kk)][lane] = (kk == j) ? a + q.w[j] : a;
-      }
-    }
+#define CPMPC_RICCATI_V_S0
+#include "sim_riccati.inc"
+    const R s = s0;
+#define CPMPC_RICCATI_GAIN(k) (k)
+#define CPMPC_RICCATI_GAIN_ACL
+#include "sim_riccati.inc"
+#undef CPMPC_RICCATI_GAIN
+#define CPMPC_RICCATI_UPDATE
+#include "sim_riccati.inc"
   }
 
   if (P0_out) {
@@ -152,39 +109,10 @@ __global__ __launch_bounds__(64) void sim_rollout_fb_kernel(int64_t B, typename 
                                                              ExtForce<R> fe_shared, const R* fext, int n_sub, R h_last, int T,
                                                              const R* x0, const R* u_nom, const R* K, const R* x0_nom,
                                                              const R* xs_nom, R u_limit, R* xs_out, R* x_final, R* us_out) {
-  constexpr int NX = M::NX;
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= B) return;
-  const typename M::Consts k = PlantConsts<R, M, PER_LANE>::get(k_arg, B, p);
-  ExtForce<R> fe = fe_shared;
-  load_ext_force<R>(fext, B, p, fe);
-  R xs[NX];
-#pragma unroll
-  for (int r = 0; r < NX; ++r) xs[r] = x0[r * B + p];
-#pragma unroll 1
-  for (int t = 0; t < T; ++t) {
-    R uu = u_nom[(int64_t)t * B + p];
-    if (K) {
-      const R* xn = (t == 0) ? x0_nom : xs_nom + (int64_t)(t - 1) * NX * B;
-      R d[NX];
-#pragma unroll
-      for (int r = 0; r < NX; ++r) d[r] = xs[r] - xn[r * B + p];
-      wrap_residual<R, M>(d);
-#pragma unroll
-      for (int r = 0; r < NX; ++r) uu = Math<R>::fma(K[((int64_t)t * NX + r) * B + p], d[r], uu);
-    }
-    uu = clampr(uu, -u_limit, u_limit);
-    if (us_out) us_out[(int64_t)t * B + p] = uu;
-    typename M::StepCache chain;
-#pragma unroll 1
-    for (int i = 0; i < n_sub; ++i) plant_sub_step<R, M>(k, fe, i, n_sub, h_last, uu, xs, chain);
-    if (xs_out)
-#pragma unroll
-      for (int r = 0; r < NX; ++r) xs_out[((int64_t)t * NX + r) * B + p] = xs[r];
-  }
-  if (x_final)
-#pragma unroll
-    for (int r = 0; r < NX; ++r) x_final[r * B + p] = xs[r];
+  const R *const kff = nullptr, *const alpha_in = nullptr;  // the iLQR's feedforward term: none here
+#define CPMPC_ROLL_LAW 1
+#define CPMPC_ROLL_COST 0
+#include "sim_roll_ticks.inc"
 }
 
 }  // namespace cpmpc

@@ -13,8 +13,8 @@ be admissible.  B = 130, sim_lqr_ref's states: lanes at the +-pi cut and beyond 
    than the reference (a discrete decision) is left out, under the same 2 % cap.  Forward: the state bound carried through the law
    once per tick, as tests/test_gpu_sim_lqr.py carries it, with alpha kff in the control's rounding; the cost's bound follows
    from the states' and controls' by the cost's own derivative plus its summation's rounding.  Every ratio is printed.
-3. identities and structure: at its own reference kff and dV are exactly 0 and K, P0 are sim_lqr's BIT FOR BIT (sim_lqr_kernel is
-   not edited); without kff, K and limit the forward pass is sim_rollout_states bit for bit; from the nominal start with alpha = 0
+3. identities and structure: at its own reference kff and dV are exactly 0 and K, P0 are sim_lqr's BIT FOR BIT (the two kernels
+   share the Riccati step's text); without kff, K and limit the forward pass is sim_rollout_states bit for bit; from the nominal start with alpha = 0
    it reproduces the nominal xs, us and cost bit for bit; outputs do not depend on which others are requested; inputs are left
    unchanged; a lane's bits do not depend on its place in the batch; a lane with non-finite data stays in its lane.  (There is no
    gT beside PT, so a window is not chained from its tail: dV and hmax are sums and maxima over the whole window anyway.)
