@@ -22,7 +22,7 @@ def __getattr__(name):
                 "sim_step_param_jacobian", "sim_step_param_vjp", "sim_rollout_states", "sim_rollout_vjp", "sim_rollout",
                 "sim_rollout_gauss_newton", "sim_identify", "sim_rollout_gauss_newton_x0", "sim_estimate_state",
                 "WindowEstimator", "sim_ekf", "StateFilter", "sim_rts", "sim_lqr", "sim_rollout_feedback",
-                "sim_ilqr_backward", "sim_ilqr_forward", "sim_ilqr"):
+                "sim_ilqr_backward", "sim_ilqr_forward", "sim_ilqr_search", "sim_ilqr"):
         from . import batch
         return getattr(batch, name)
     raise AttributeError(name)

@@ -1595,8 +1595,51 @@ def sim_ilqr_forward(params, dt, state, u_nom, kff, K, x0_nom, xs_nom, x_ref, u_
 ILQR_ARMIJO = 1e-4   # a step is accepted where the cost falls by at least this share of the model's prediction
 
 
+def sim_ilqr_search(params, dt, state, u_nom, xs_nom, cost_nom, kff, K, dV, x_ref, u_ref, q, r, terminal=None, trials=6,
+                    armijo=ILQR_ARMIJO, u_limit=float("inf"), fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single",
+                    want=("xs", "us", "cost", "alpha")):
+    """The line search of one iLQR iteration in ONE launch (include/cpmpc.h: cpmpc_sim_ilqr_search_batch): every problem walks
+    its own trial ladder on sim_ilqr_forward's roll, from the nominal trajectory state [nx, B] (the start, of the nominal too:
+    there is no x0_nom), u_nom [T, B], xs_nom [T, nx, B] (always required) with cost cost_nom [B], under sim_ilqr_backward's
+    kff [T, B], K [T, nx, B] (or None) and dV [2, B]:
+        alpha = 1; up to `trials` (1..32) times: roll under u_t = clamp(u_nom[t] + alpha kff[t] + K[t] . wrap(x_t - x_nom_t)),
+        accept where pred = dV[0] alpha + dV[1] alpha^2 < 0 and J_try - cost_nom <= armijo pred, else halve alpha.
+    A problem leaves the ladder when it has decided, so the launch costs between one roll and `trials` rolls.  The decisions
+    are those of the ladder of sim_ilqr_forward calls that sim_ilqr's default loop runs, bit for bit, and an accepted problem's
+    xs, x_final, us and cost are sim_ilqr_forward's at its alpha, bit for bit.  A failed problem keeps its nominal BY COPY
+    (alpha 0): what a forward call with alpha = 0 returns for finite data; where kff, K or dV of a problem is not finite while
+    its nominal is, that call would poison it through 0 . NaN, and the search instead fails it and leaves its trajectory for a
+    retry under a larger mu.  A problem whose nominal or cost_nom is itself non-finite returns that; no other problem is
+    affected.  x_ref, u_ref, q, r, terminal: the cost, as sim_ilqr_backward's; params, dt and the forces as
+    sim_rollout_states'.
+
+    Returns a dict with the entries named in `want`,
+        "xs" [T, nx, B],  "x_final" [nx, B],  "us" [T, B],  "cost" [B],  "alpha" [B] the step taken, 0: none."""
+    want = _want_tuple(want, ("xs", "x_final", "us", "cost", "alpha"))
+    m, nx, npar = dims = _model_dims(model)
+    dtp = state.dtype
+    a = capi.SimIlqrSearch(struct_size=C.sizeof(capi.SimIlqrSearch), r=float(r), u_limit=float(u_limit), trials=int(trials),
+                           armijo=float(armijo))
+    B, T, host, _, _held = _plant_inputs(dims, state, u_nom, params, fext, f_base, f_mass, a, ticks=True, u_field="u_nom")
+    for name, t, shape in (("xs_nom", xs_nom, (T, nx, B)), ("cost_nom", cost_nom, (B,)), ("kff", kff, (T, B)), ("dV", dV, (2, B))):
+        if t is None:
+            raise ValueError("%s is required" % name)
+        _require_cuda_tensor(t, name, dtp, shape)
+        setattr(a, name, t.data_ptr())
+    if K is not None:
+        _require_cuda_tensor(K, "K", dtp, (T, nx, B))
+        a.K = K.data_ptr()
+    _cost_held = _ilqr_cost(a, nx, B, T, dtp, state.device, x_ref, u_ref, q, terminal)
+    res = _alloc_outputs(a, want, {"xs": ("xs", (T, nx, B)), "x_final": ("x_final", (nx, B)), "us": ("us", (T, B)),
+                                   "cost": ("cost", (B,)), "alpha": ("alpha", (B,))}, dtp, state.device)
+    with torch.cuda.device(state.device):
+        capi.check(capi.load().cpmpc_sim_ilqr_search_batch(m, _CAPI_DTYPE[dtp], B, host, float(dt), T, C.byref(a),
+                                                           _stream_ptr()))
+    return res
+
+
 def sim_ilqr(params, dt, state, u_init, x_ref, q, r, terminal=None, u_ref=None, u_limit=float("inf"), iterations=10, trials=6,
-             mu_init=0.0, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single"):
+             mu_init=0.0, fext=None, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), model="single", search="trials"):
     """Iterative LQR on the plant's own tick map, every problem in lock-step with its own line search and regularisation: fixed
     counts, elementwise torch between the launches, NO host synchronisation.  From state [nx, B] and the controls
     u_init [T, B] (clamped to +-u_limit by the first rollout), for the cost of sim_ilqr_backward:
@@ -1609,6 +1652,10 @@ def sim_ilqr(params, dt, state, u_init, x_ref, q, r, terminal=None, u_ref=None, 
         failed -> max(10 mu, 1e-3).
     So J never increases on any problem.  A closing sim_ilqr_backward at the returned trajectory (with the returned mu) gives
     the gains that track it and its stationarity measure.
+    search="trials" (the default) is that loop; search="fused" replaces the `trials` + 1 forward calls of an iteration and the
+    torch between them by ONE sim_ilqr_search call (`trials` <= 32 there), in which a problem stops rolling once it has
+    decided: the same decisions and the same entries bit for bit on finite data; where a problem's kff, K or dV is not finite
+    the fused search fails it and keeps its trajectory (sim_ilqr_search).  The mu update is the same torch in both.
 
     Returns a dict: "u" [T, B], "xs" [T, nx, B], "K" [T, nx, B], "cost" [B], "cost_history" [iterations + 1, B] (row 0: of
     u_init), "hmax" [B], "mu" [B], "accepted" [iterations, B] bool."""
@@ -1617,6 +1664,10 @@ def sim_ilqr(params, dt, state, u_init, x_ref, q, r, terminal=None, u_ref=None, 
         raise ValueError("iterations must be >= 0 and trials >= 1")
     if not float(mu_init) >= 0.0:
         raise ValueError("mu_init must be >= 0")
+    if search not in ("trials", "fused"):
+        raise ValueError("search must be 'trials' or 'fused'")
+    if search == "fused" and trials > 32:
+        raise ValueError("search='fused' takes trials <= 32")
     _, nx, _ = _model_dims(model)
     _require_cuda_tensor(state, "state", state.dtype)
     _require_cuda_tensor(u_init, "u_init", state.dtype)
@@ -1633,18 +1684,23 @@ def sim_ilqr(params, dt, state, u_init, x_ref, q, r, terminal=None, u_ref=None, 
     history, accepted = [J], []
     for _ in range(iterations):
         bw = sim_ilqr_backward(params, dt, state, u, xs, ref, u_ref, q, r, mu=mu, want=("K", "kff", "dV"), **cost_kw)
-        dV1, dV2 = bw["dV"][0], bw["dV"][1]
-        alpha = torch.ones((B,), dtype=dtp, device=dev)
-        done = torch.zeros((B,), dtype=torch.bool, device=dev)
-        for _ in range(trials):
-            J_try = sim_ilqr_forward(params, dt, state, u, bw["kff"], bw["K"], state, xs, ref, u_ref, q, r, alpha=alpha,
-                                     want="cost", **cost_kw)["cost"]
-            pred = dV1 * alpha + dV2 * alpha * alpha
-            done = done | ((pred < 0) & (J_try - J <= ILQR_ARMIJO * pred))
-            alpha = torch.where(done, alpha, 0.5 * alpha)
-        alpha = torch.where(done, alpha, torch.zeros_like(alpha))
-        fin = sim_ilqr_forward(params, dt, state, u, bw["kff"], bw["K"], state, xs, ref, u_ref, q, r, alpha=alpha,
-                               want=("xs", "us", "cost"), **cost_kw)
+        if search == "fused":
+            fin = sim_ilqr_search(params, dt, state, u, xs, J, bw["kff"], bw["K"], bw["dV"], ref, u_ref, q, r, trials=trials,
+                                  want=("xs", "us", "cost", "alpha"), **cost_kw)
+            done = fin["alpha"] > 0
+        else:
+            dV1, dV2 = bw["dV"][0], bw["dV"][1]
+            alpha = torch.ones((B,), dtype=dtp, device=dev)
+            done = torch.zeros((B,), dtype=torch.bool, device=dev)
+            for _ in range(trials):
+                J_try = sim_ilqr_forward(params, dt, state, u, bw["kff"], bw["K"], state, xs, ref, u_ref, q, r, alpha=alpha,
+                                         want="cost", **cost_kw)["cost"]
+                pred = dV1 * alpha + dV2 * alpha * alpha
+                done = done | ((pred < 0) & (J_try - J <= ILQR_ARMIJO * pred))
+                alpha = torch.where(done, alpha, 0.5 * alpha)
+            alpha = torch.where(done, alpha, torch.zeros_like(alpha))
+            fin = sim_ilqr_forward(params, dt, state, u, bw["kff"], bw["K"], state, xs, ref, u_ref, q, r, alpha=alpha,
+                                   want=("xs", "us", "cost"), **cost_kw)
         u, xs, J = fin["us"], fin["xs"], fin["cost"]
         down = mu / 10.0
         mu = torch.where(done, torch.where(down < 1e-6, torch.zeros_like(mu), down), torch.clamp(10.0 * mu, min=1e-3))
@@ -1895,11 +1951,11 @@ class BatchSimulator:
         return res["xs"], res["us"]
 
     def ilqr(self, params, dt, u_init, x_ref, q, r, terminal=None, u_ref=None, u_limit=float("inf"), iterations=10, trials=6,
-             mu_init=0.0, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
+             mu_init=0.0, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None, search="trials"):
         """sim_ilqr from the simulator's own state, which is read and NOT advanced: a plan for the T ticks ahead (its dict)."""
         return sim_ilqr(params.detach() if isinstance(params, torch.Tensor) else params, dt, self.state, u_init, x_ref, q, r,
                         terminal=terminal, u_ref=u_ref, u_limit=u_limit, iterations=iterations, trials=trials, mu_init=mu_init,
-                        fext=fext, f_base=f_base, f_mass=f_mass, model=self.model)
+                        fext=fext, f_base=f_base, f_mass=f_mass, model=self.model, search=search)
 
     def rollout_differentiable(self, params, dt, u, f_base=(0.0, 0.0), f_mass=(0.0, 0.0), fext=None):
         """rollout() with a backward: xs = sim_rollout(params, dt, self.state, u, ...) is returned, attached to the autograd

@@ -53,6 +53,7 @@ SYMBOLS = [
     "cpmpc_sim_rollout_batch", "cpmpc_sim_rollout_vjp_batch", "cpmpc_sim_rollout_gn_batch",
     "cpmpc_sim_rollout_gn_x0_batch", "cpmpc_sim_ekf_batch", "cpmpc_sim_rts_batch", "cpmpc_sim_rts_work_rows",
     "cpmpc_sim_lqr_batch", "cpmpc_sim_rollout_fb_batch", "cpmpc_sim_ilqr_backward_batch", "cpmpc_sim_ilqr_forward_batch",
+    "cpmpc_sim_ilqr_search_batch",
 ]
 
 
@@ -489,6 +490,42 @@ class SimIlqrForward(C.Structure):
     ]
 
 
+class SimIlqrSearch(C.Structure):
+    """cpmpc_sim_ilqr_search: device pointers of cpmpc_sim_ilqr_search_batch; the nominal x0, u_nom [T][B], xs_nom (always
+    required) and cost_nom [B], the backward pass's kff, K (null: no feedback) and dV [2][B], the reference, dyn and PT are
+    read; trials in 1..32 and armijo in (0, 1) by value; u_limit is the clamp (infinity: none); xs, x_final, us, cost and
+    alpha (the step taken, 0: none) are nullable outputs."""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("x0", C.c_void_p),
+        ("u_nom", C.c_void_p),
+        ("fext_host", C.POINTER(C.c_double)),
+        ("fext", C.c_void_p),
+        ("dyn", C.c_void_p),
+        ("xs_nom", C.c_void_p),
+        ("cost_nom", C.c_void_p),
+        ("kff", C.c_void_p),
+        ("K", C.c_void_p),
+        ("dV", C.c_void_p),
+        ("trials", C.c_int32),
+        ("reserved", C.c_int32),
+        ("armijo", C.c_double),
+        ("u_limit", C.c_double),
+        ("x0_ref", C.c_void_p),
+        ("xs_ref", C.c_void_p),
+        ("u_ref", C.c_void_p),
+        ("q_host", C.POINTER(C.c_double)),
+        ("r", C.c_double),
+        ("PT", C.c_void_p),
+        ("qf_host", C.POINTER(C.c_double)),
+        ("xs", C.c_void_p),
+        ("x_final", C.c_void_p),
+        ("us", C.c_void_p),
+        ("cost", C.c_void_p),
+        ("alpha", C.c_void_p),
+    ]
+
+
 class CpmpcError(RuntimeError):
     def __init__(self, code, text):
         super().__init__("cpmpc error %d: %s" % (code, text))
@@ -631,6 +668,7 @@ def load():
     L.cpmpc_sim_rollout_fb_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimRolloutFb), vp]
     L.cpmpc_sim_ilqr_backward_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimIlqrBackward), vp]
     L.cpmpc_sim_ilqr_forward_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimIlqrForward), vp]
+    L.cpmpc_sim_ilqr_search_batch.argtypes = [i32, i32, i64, _dp, dbl, i32, C.POINTER(SimIlqrSearch), vp]
     _lib = L
     return L
 

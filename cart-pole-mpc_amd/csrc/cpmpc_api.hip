@@ -1333,6 +1333,42 @@ extern "C" int cpmpc_sim_ilqr_forward_batch(int model, int dtype, int64_t B, con
   });
 }
 
+static int check_sim_ilqr_search_args(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                      const cpmpc_sim_ilqr_search* a) {
+  int rc = check_fb_rollout_common("cpmpc_sim_ilqr_search", a, dyn_shared_host, dt, T, model, dtype, B);
+  if (rc) return rc;
+  if (!a->xs && !a->x_final && !a->us && !a->cost && !a->alpha)
+    return fail(CPMPC_ERR_INVALID_ARG, "null argument (no output asked for)");
+  const size_t nx = (size_t)model_nx(model), np = (size_t)model_np(model), nt = (size_t)T;
+  rc = check_sim_ilqr_cost(a, nx);
+  if (rc) return rc;
+  if (!a->xs_nom) return fail(CPMPC_ERR_INVALID_ARG, "null argument (xs_nom: always required, row T-1 is a failed problem's x_final)");
+  if (!a->cost_nom) return fail(CPMPC_ERR_INVALID_ARG, "null argument (cost_nom)");
+  if (!a->kff) return fail(CPMPC_ERR_INVALID_ARG, "null argument (kff)");
+  if (!a->dV) return fail(CPMPC_ERR_INVALID_ARG, "null argument (dV)");
+  if (a->trials < 1 || a->trials > 32) return fail(CPMPC_ERR_INVALID_ARG, "trials is %d, must be in 1..32", (int)a->trials);
+  if (a->reserved != 0) return fail(CPMPC_ERR_INVALID_ARG, "reserved is %d, must be 0", (int)a->reserved);
+  if (!(a->armijo > 0.0 && a->armijo < 1.0)) return fail(CPMPC_ERR_INVALID_ARG, "armijo must be finite and in (0, 1)");
+  // xs and us are written during the trials: every input is still read after the first store
+  const ArraySpan outs[5] = {{a->xs, nt * nx, "xs"}, {a->x_final, nx, "x_final"}, {a->us, nt, "us"}, {a->cost, 1, "cost"},
+                             {a->alpha, 1, "alpha"}};
+  const ArraySpan ins[13] = {{a->x0, nx, "x0"},         {a->u_nom, nt, "u_nom"},        {a->fext, 4, "fext"},
+                             {a->dyn, np, "dyn"},       {a->xs_nom, nt * nx, "xs_nom"}, {a->cost_nom, 1, "cost_nom"},
+                             {a->kff, nt, "kff"},       {a->K, nt * nx, "K"},           {a->dV, 2, "dV"},
+                             {a->x0_ref, nx, "x0_ref"}, {a->xs_ref, nt * nx, "xs_ref"}, {a->u_ref, nt, "u_ref"},
+                             {a->PT, nx * nx, "PT"}};
+  return check_no_overlap(outs, ins, row_bytes(dtype, B));
+}
+
+extern "C" int cpmpc_sim_ilqr_search_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                           const cpmpc_sim_ilqr_search* a, void* stream) {
+  int rc = check_sim_ilqr_search_args(model, dtype, B, dyn_shared_host, dt, T, a);
+  if (rc) return rc;
+  return run_plant_call(dt, false, [&](int n_sub, double h_last) {
+    engine_for(dtype, model)->sim_ilqr_search(B, dyn_shared_host, n_sub, h_last, T, a, (hipStream_t)stream);
+  });
+}
+
 // ------------------------------------------------------------------------------------------------
 // feedback gains
 // ------------------------------------------------------------------------------------------------

@@ -261,6 +261,10 @@ struct Engine {
   // launch: xs, x_final, us, cost of `a` that are not null (sim_ilqr_kernels.hpp)
   void (*sim_ilqr_forward)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
                            const cpmpc_sim_ilqr_forward* a, hipStream_t stream);
+  // the line search of one iLQR iteration in one launch, each problem halving its own step until its rolled cost passes the
+  // Armijo test: xs, x_final, us, cost, alpha of `a` that are not null (sim_ilqr_kernels.hpp)
+  void (*sim_ilqr_search)(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                          const cpmpc_sim_ilqr_search* a, hipStream_t stream);
 };
 // (functions, not namespace-scope tables: hipcc would emit a constant table for the device side as well)
 CPMPC_HIDDEN const Engine* cpmpc_engine_f32_single();

@@ -715,6 +715,21 @@ static void sim_ilqr_forward_impl(int64_t B, const double* dyn_shared_host, int 
   });
 }
 
+template <typename R, typename M>
+static void sim_ilqr_search_impl(int64_t B, const double* dyn_shared_host, int n_sub, double h_last, int T,
+                                 const cpmpc_sim_ilqr_search* a, hipStream_t stream) {
+  const TrackWeights<R, M::NX> w(a->q_host, a->qf_host);
+  with_per_lane(a->dyn != nullptr, [&](auto per_lane) {
+    constexpr bool PL = decltype(per_lane)::value;
+    hipLaunchKernelGGL((sim_ilqr_search_kernel<R, M, PL>), grid_for(B), dim3(64), 0, stream, B,
+                       plant_consts_arg<R, M, PL>(dyn_shared_host, a->dyn), ext_from_host<R>(a->fext_host), (const R*)a->fext,
+                       n_sub, (R)h_last, T, (const R*)a->x0, (const R*)a->u_nom, (const R*)a->xs_nom, (const R*)a->cost_nom,
+                       (const R*)a->kff, (const R*)a->K, (const R*)a->dV, (int)a->trials, (R)a->armijo, (R)a->u_limit,
+                       (const R*)a->x0_ref, (const R*)a->xs_ref, (const R*)a->u_ref, w.q, (R)a->r, (const R*)a->PT, w.qf,
+                       (R*)a->xs, (R*)a->x_final, (R*)a->us, (R*)a->cost, (R*)a->alpha);
+  });
+}
+
 // ---- feedback gains and the sensitivities of the plan ----------------------------------------------------------------
 // All four calls start alike: the arguments of a linearisation at z, then launch_linearize (a caller's z goes through the
 // step buffers dzx / dzu, which hold no state between calls; z == NULL: the warm start itself, read only), then one lane
@@ -858,7 +873,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
 // swapped unseen, and the order of engine.hpp's declarations is free.  A new member gets a line here.
 #define CPMPC_DEFINE_ENGINE(NAME, R, M)                                                                               \
   const Engine* NAME() {                                                                                              \
-    static_assert(sizeof(Engine) == 29 * sizeof(void*), "an entry point of engine.hpp has no line below");            \
+    static_assert(sizeof(Engine) == 30 * sizeof(void*), "an entry point of engine.hpp has no line below");            \
     static const Engine e = [] {                                                                                      \
       Engine t{};                                                                                                     \
       t.step_batch = &step_batch_impl<R, M>;              t.host_chunk_begin = &host_chunk_begin<R, M>;               \
@@ -875,7 +890,7 @@ static int debug_read_impl(int which, unsigned long long* out) {
       t.sim_rollout_gn_x0 = &sim_rollout_gn_x0_impl<R, M>; t.sim_ekf = &sim_ekf_impl<R, M>;                           \
       t.sim_rts = &sim_rts_impl<R, M>;                    t.sim_lqr = &sim_lqr_impl<R, M>;                            \
       t.sim_rollout_fb = &sim_rollout_fb_impl<R, M>;      t.sim_ilqr_backward = &sim_ilqr_backward_impl<R, M>;        \
-      t.sim_ilqr_forward = &sim_ilqr_forward_impl<R, M>;                                                              \
+      t.sim_ilqr_forward = &sim_ilqr_forward_impl<R, M>;  t.sim_ilqr_search = &sim_ilqr_search_impl<R, M>;            \
       return t;                                                                                                       \
     }();                                                                                                              \
     return &e;                                                                                                        \

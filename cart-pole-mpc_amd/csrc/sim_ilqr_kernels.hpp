@@ -1,4 +1,5 @@
-// sim_ilqr_kernels.hpp -- one iteration of an iterative LQR on the plant's own tick map, as two kernels: the backward Riccati
+// sim_ilqr_kernels.hpp -- one iteration of an iterative LQR on the plant's own tick map, as two kernels and a third that runs
+// the line search between them in one launch: the backward Riccati
 // pass with a feedforward term, the exact treatment of the control's box limit and the predicted cost change; and the forward
 // pass that applies alpha . k_t and sums the cost on the device.  The plant has ONE input, so the box QP of control-limited DDP
 // is a scalar clamp and, as in sim_lqr_kernel (sim_track_kernels.hpp), no matrix is inverted.
@@ -40,6 +41,26 @@
 // kff and K are each nullable; with both NULL and u_limit = +inf it is sim_rollout_kernel bit for bit, with its cost.  alpha
 // NULL means 1.  From the nominal start with alpha = 0 the deviation is exactly 0 at every tick and the nominal controls (a
 // forward call's own, already inside the limit) and states come back bit for bit.
+//
+// sim_ilqr_search_kernel: the same body with its third part compiled in -- the whole line search of an iteration in one launch,
+// one problem per lane, nothing crossing lanes.  The nominal start is x0 itself (a line search compares costs from one start):
+//     alpha = 1 ; accepted = false
+//     for j in 0 .. trials-1 while not accepted:
+//         roll T ticks under the law above, summing J_try           the roll stores xs, us as it goes, for this lane only
+//         pred = dV1 alpha + dV2 alpha^2
+//         accepted = pred < 0 and J_try - cost_nom <= armijo pred
+//         if not accepted: alpha = alpha / 2
+//     accepted: xs, us, x_final are in place ; cost = J_try ; alpha_out = alpha
+//     else:     xs = xs_nom, us = u_nom, x_final = xs_nom[T-1], cost = cost_nom, alpha_out = 0            (a copy)
+// The ladder only halves, so alpha is a power of two: dV1 alpha and dV2 alpha alpha are exact and pred rounds once whether or
+// not the compiler contracts it; J_try - cost_nom and armijo pred are each rounded on their own and compared.  The decision is
+// therefore, bit for bit, the one a ladder of sim_ilqr_forward_kernel calls with elementwise arithmetic between them takes,
+// and an accepted lane's outputs are that kernel's at the lane's alpha.  A decided lane is masked off and the wave leaves with
+// its last lane; trials <= 32 bounds the run time.  Outputs may not overlap inputs, so a rejected trial's stores are simply
+// overwritten.  A FAILED LANE KEEPS ITS NOMINAL BY COPY: for finite data that is what a forward call with alpha = 0 yields (the
+// identity above); it differs on purpose where kff, K or dV of a lane is not finite while its nominal is: alpha = 0 would
+// poison such a lane through 0 . NaN, the search fails it and it keeps its trajectory for a retry under a larger mu.  A lane
+// whose nominal or cost_nom is itself non-finite returns that.  No lane affects another.
 #pragma once
 #include "sim_track_kernels.hpp"
 
@@ -228,6 +249,23 @@ __global__ __launch_bounds__(64) void sim_ilqr_forward_kernel(
     R* xs_out, R* x_final, R* us_out, R* cost_out) {
 #define CPMPC_ROLL_LAW 1
 #define CPMPC_ROLL_COST 1
+#define CPMPC_ROLL_SEARCH 0
+#include "sim_roll_ticks.inc"
+}
+
+// The nominal trajectory x0, u_nom [T][B], xs_nom [T][NX][B] (ALWAYS required: row T-1 is read for a failed lane's copy) and its
+// cost cost_nom [B]; the backward pass's kff [T][B], K [T][NX][B] or NULL, dV [2][B]; the reference and the weights as the
+// forward kernel's; trials in 1..32 and armijo by value.  Outputs, each written only where its pointer is given and none
+// overlapping an input: xs_out [T][NX][B], x_final [NX][B], us_out [T][B], cost_out [B], alpha_out [B] the step taken, 0: none.
+template <typename R, typename M, bool PER_LANE>
+__global__ __launch_bounds__(64) void sim_ilqr_search_kernel(
+    int64_t B, typename PlantConsts<R, M, PER_LANE>::Arg k_arg, ExtForce<R> fe_shared, const R* fext, int n_sub, R h_last, int T,
+    const R* x0, const R* u_nom, const R* xs_nom, const R* cost_nom, const R* kff, const R* K, const R* dV, int trials, R armijo,
+    R u_limit, const R* x0_ref, const R* xs_ref, const R* u_ref, StateWeights<R, M::NX> q, R rw, const R* PT,
+    StateWeights<R, M::NX> qf, R* xs_out, R* x_final, R* us_out, R* cost_out, R* alpha_out) {
+#define CPMPC_ROLL_LAW 1
+#define CPMPC_ROLL_COST 1
+#define CPMPC_ROLL_SEARCH 1
 #include "sim_roll_ticks.inc"
 }
 

@@ -38,6 +38,7 @@ __global__ __launch_bounds__(64) void sim_rollout_kernel(int64_t B, typename Pla
                                                           const R* x0, const R* u_nom, R* xs_out, R* x_final) {
 #define CPMPC_ROLL_LAW 0
 #define CPMPC_ROLL_COST 0
+#define CPMPC_ROLL_SEARCH 0
 #include "sim_roll_ticks.inc"
 }
 

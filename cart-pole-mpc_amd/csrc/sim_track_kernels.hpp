@@ -112,6 +112,7 @@ __global__ __launch_bounds__(64) void sim_rollout_fb_kernel(int64_t B, typename 
   const R *const kff = nullptr, *const alpha_in = nullptr;  // the iLQR's feedforward term: none here
 #define CPMPC_ROLL_LAW 1
 #define CPMPC_ROLL_COST 0
+#define CPMPC_ROLL_SEARCH 0
 #include "sim_roll_ticks.inc"
 }
 

@@ -931,6 +931,66 @@ typedef struct cpmpc_sim_ilqr_forward {
 int cpmpc_sim_ilqr_forward_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
                                  const cpmpc_sim_ilqr_forward* a, void* stream);
 
+/* The LINE SEARCH of one iteration in ONE launch: every problem walks its own trial ladder on the forward pass above, from the
+ * nominal trajectory (x0, u_nom, xs_nom) with cost cost_nom, under cpmpc_sim_ilqr_backward_batch's kff, K (or NULL) and dV.
+ * The nominal start is x0 itself -- there is no x0_nom, a line search compares costs from one start:
+ *     alpha = 1 ; accepted = false
+ *     for j in 0 .. trials-1 while not accepted:
+ *         roll T ticks under u_t = clamp(u_nom[t] + alpha kff[t] + K[t] . wrap(x_t - x_nom_t), +-u_limit), summing J_try
+ *         pred = dV[0] alpha + dV[1] alpha^2
+ *         accepted = pred < 0 and J_try - cost_nom <= armijo pred
+ *         if not accepted: alpha = alpha / 2
+ *     accepted: xs, us, x_final of that roll ; cost = J_try ; alpha = the step taken
+ *     else:     xs = xs_nom, us = u_nom, x_final = xs_nom[T-1], cost = cost_nom, alpha = 0              (a COPY)
+ * SIGN CONVENTION of dV: the backward pass's, alpha dV[0] + alpha^2 dV[1] is the predicted CHANGE of J (negative: a decrease);
+ * a problem whose prediction is not negative takes no step.  The ladder only halves, so alpha is a power of two, pred is
+ * rounded once and the two sides of the test are each rounded on their own: THE DECISIONS ARE THOSE OF THE TRIAL LADDER written
+ * with cpmpc_sim_ilqr_forward_batch calls and elementwise arithmetic in `dtype` between them, bit for bit, and an accepted
+ * problem's xs, x_final, us and cost are that call's at its alpha, bit for bit.  A problem leaves the ladder when it has
+ * decided; one launch costs between one roll (every problem of a wave accepts at once) and `trials` rolls.
+ * A FAILED PROBLEM KEEPS ITS NOMINAL BY COPY.  For finite data that is what a forward call with alpha = 0 returns.  It differs
+ * on purpose where kff, K or dV of a problem is NOT FINITE while its nominal is finite: a forward call with alpha = 0 would
+ * poison the problem through 0 . NaN; the search fails it (alpha = 0) and it keeps its trajectory, for a retry under a larger
+ * mu.  A problem whose nominal or cost_nom is itself non-finite returns that.  No other problem is affected.
+ *     xs [T][NX][B], x_final [NX][B], us [T][B], cost [B], alpha [B] (0: no step);
+ * each is nullable, at least one must be given, and each is bitwise the same whichever others are asked for.  xs_nom is ALWAYS
+ * required, for T = 1 too: row T-1 is read for the copy.  xs and us are written during the trials, so NO OUTPUT MAY OVERLAP AN
+ * INPUT ARRAY.  dt = 0: the state stays, us and cost as written.
+ * Device pointers in `dtype`; ONE launch on `stream`, no host synchronisation, no allocation.  Everything the forward call
+ * refuses, and xs_nom, cost_nom, kff or dV == NULL, trials outside 1..32, reserved != 0, armijo not finite or not in (0, 1), no output ->
+ * CPMPC_ERR_INVALID_ARG, before any device is needed. */
+typedef struct cpmpc_sim_ilqr_search {
+  uint64_t struct_size;   /* = sizeof(cpmpc_sim_ilqr_search) */
+  const void* x0;         /* [NX][B], read only: the start, of the nominal too */
+  const void* u_nom;      /* [T][B] the nominal controls */
+  const double* fext_host;/* shared {fb.x, fb.y, fm.x, fm.y} or NULL */
+  const void* fext;       /* [4][B] or NULL (takes precedence) */
+  const void* dyn;        /* [NP][B] per-problem parameters or NULL (then dyn_shared_host) */
+  const void* xs_nom;     /* [T][NX][B] the nominal states; always required */
+  const void* cost_nom;   /* [B] the nominal's cost */
+  const void* kff;        /* [T][B] feedforward terms */
+  const void* K;          /* [T][NX][B] gains or NULL: no feedback */
+  const void* dV;         /* [2][B] the predicted change's two coefficients */
+  int32_t trials;         /* 1..32 */
+  int32_t reserved;       /* must be 0: the padding behind trials, spelled out */
+  double armijo;         /* in (0, 1): the share of the prediction a step must reach */
+  double u_limit;         /* > 0; +infinity: no clamp */
+  const void* x0_ref;     /* [NX][B] the target of x0 */
+  const void* xs_ref;     /* [T][NX][B] the targets of xs; row T-1 is the terminal target */
+  const void* u_ref;      /* [T][B] the controls' targets or NULL: zeros */
+  const double* q_host;   /* NX state weights >= 0, or NULL: ones */
+  double r;               /* the control weight, finite and > 0 */
+  const void* PT;         /* [NX*NX][B] terminal cost or NULL; the lower triangle is read */
+  const double* qf_host;  /* NX terminal weights >= 0 used where PT is NULL, or NULL: q_host's */
+  void* xs;               /* [T][NX][B] or NULL */
+  void* x_final;          /* [NX][B] or NULL */
+  void* us;               /* [T][B] or NULL */
+  void* cost;             /* [B] or NULL */
+  void* alpha;            /* [B] or NULL */
+} cpmpc_sim_ilqr_search;
+int cpmpc_sim_ilqr_search_batch(int model, int dtype, int64_t B, const double* dyn_shared_host, double dt, int T,
+                                const cpmpc_sim_ilqr_search* a, void* stream);
+
 /* ---- several GPUs from ONE process ------------------------------------------------------------------ */
 /* The reference is single-threaded and single-device; a batch of independent controllers shards
  * embarrassingly, so this is new surface: one `cpmpc_sharded` owns one solver handle + one stream per shard, a shard
