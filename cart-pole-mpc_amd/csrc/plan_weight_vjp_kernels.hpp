@@ -53,6 +53,19 @@
 
 namespace cpmpc {
 
+// wrap_angles for the two residuals this kernel reads, c_init = z_0 - x0 and the terminal error: an angle already in
+// (-pi, pi] is left as it is.  mod_pi sends a negative one through + 2 pi, - 2 pi, which changes nothing in exact arithmetic
+// and costs half an ulp of 2 pi -- 2.4e-7 in float -- on a difference of two floats that was exact.  The solver never sees
+// that (its QP is as well posed around the moved residual), but g_tw of a pole-angle row is proportional to that row's
+// residual: in the float handles its error was five times that of the other outputs ("Feedback gains").
+// The cut is mod_pi's: -pi itself and everything outside the interval still go through it.
+template <typename R, typename M>
+__device__ __forceinline__ void wrap_angles_in_place(R (&x)[M::NX]) {
+  constexpr R pi = static_cast<R>(3.14159265358979323846);
+#pragma unroll
+  for (int t = 1; t < M::NQ; ++t) x[t] = (x[t] > -pi && x[t] <= pi) ? x[t] : mod_pi(x[t]);
+}
+
 template <typename R, typename M, bool WIDEQ>
 __global__ __launch_bounds__(64) void plan_weight_vjp_kernel(const SolverArgs<R, M> a, const XV<R, M::NX>* __restrict__ zx_in,
                                                               const R* __restrict__ zu_in, const R* __restrict__ u_prev_in,
@@ -87,12 +100,12 @@ __global__ __launch_bounds__(64) void plan_weight_vjp_kernel(const SolverArgs<R,
     unpack<R, NX>(zx_in[p], z0);
 #pragma unroll
     for (int t = 0; t < NX; ++t) ci[t] = z0[t] - a.x0[t * a.B + p];
-    wrap_angles<R, M>(ci);
+    wrap_angles_in_place<R, M>(ci);
     unpack<R, NX>(zx_in[(int64_t)(S - 1) * st + p], zt);
 #pragma unroll
     for (int t = 0; t < NX; ++t) e_term[t] = zt[t] - a.term_tgt[t];
     if (a.set_point) e_term[0] = zt[0] - a.set_point[p];
-    wrap_angles<R, M>(e_term);
+    wrap_angles_in_place<R, M>(e_term);
 #pragma unroll
     for (int t = 0; t < NX; ++t) hv[t] = WO::prod(Rw[t], e_term[t]);  // + the weighted free response, added after sweep 1
   }

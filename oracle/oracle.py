@@ -243,6 +243,9 @@ def lib_f32():
         L.orcf_closed_loop_d.argtypes = [C.c_int, C.POINTER(OptParams), C.POINTER(SolverOpts), _dp, C.c_double, C.c_int64,
                                          _dp, C.c_int, bp, bp, _dp, C.c_int]
         L.orcf_closed_loop_d.restype = C.c_int
+        fp = C.POINTER(C.c_float)
+        L.orcf_problem_eval_model.argtypes = [C.c_int, C.POINTER(OptParams), fp, fp, C.c_float, C.c_float, fp, fp, fp, fp, fp]
+        L.orcf_problem_eval_model.restype = None
         _lib_f32 = L
     return _lib_f32
 
@@ -431,6 +434,22 @@ def problem_shape_model(model, p):
     d, e, c = C.c_int(), C.c_int(), C.c_int()
     lib().orc_problem_shape_model(MODELS[model], C.byref(p), C.byref(d), C.byref(e), C.byref(c))
     return d.value, e.value, c.value
+
+
+def problem_eval_f32(model, p, dyn, x_current, set_point, u_prev, z):
+    """orcf_problem_eval_model: (r, c, J, A) of either model evaluated in SINGLE precision (oracle/cpmpc_oracle_f32.c), the
+    inputs rounded to float, the outputs returned as float64 arrays holding float values."""
+    m = MODELS[model]
+    dim, n_eq, n_cost = problem_shape_model(m, p)
+    fp = C.POINTER(C.c_float)
+    dyn, x_current, z = (np.ascontiguousarray(a, dtype=np.float32) for a in (dyn, x_current, z))
+    assert z.size == dim and x_current.size == model_nx(m) and dyn.size == model_np(m)
+    r, c = np.zeros(max(n_cost, 1), dtype=np.float32), np.zeros(n_eq, dtype=np.float32)
+    J, A = np.zeros((max(n_cost, 1), dim), dtype=np.float32), np.zeros((n_eq, dim), dtype=np.float32)
+    lib_f32().orcf_problem_eval_model(m, C.byref(p), dyn.ctypes.data_as(fp), x_current.ctypes.data_as(fp), float(set_point),
+                                      float(u_prev), z.ctypes.data_as(fp), r.ctypes.data_as(fp), c.ctypes.data_as(fp),
+                                      J.ctypes.data_as(fp), A.ctypes.data_as(fp))
+    return tuple(a.astype(np.float64) for a in (r[:n_cost], c, J[:n_cost], A))
 
 
 def sim_step_model(model, params, dt, u, state):

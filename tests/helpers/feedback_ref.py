@@ -109,11 +109,17 @@ def feedback_gain_qp_diff(orc, p, dyn, z, model="single"):
     return K, codes, float(np.abs(dz0).max())
 
 
-def blocks_of(orc, p, dyn, z, model="single"):
-    """(Phi [S-1, NX, NX], Gam [N, NX]) read from the shooting rows of the oracle's A at z."""
+def blocks_of(orc, p, dyn, z, model="single", precision="f64"):
+    """(Phi [S-1, NX, NX], Gam [N, NX]) read from the shooting rows of the oracle's A at z.  precision="f32": of the
+    single-precision oracle's A (orc.problem_eval_f32: the linearisation itself computed in float, not the double blocks
+    rounded)."""
     nx, N, sp, S = _shape(orc, model, p)
     z = np.asarray(z, dtype=np.float64)
-    _, _, _, A = problem_eval(orc, model, p, dyn, z[:nx], 0.0, 0.0, z)
+    assert precision in ("f64", "f32"), precision
+    if precision == "f32":
+        _, _, _, A = orc.problem_eval_f32(model, p, dyn, z[:nx], 0.0, 0.0, z)
+    else:
+        _, _, _, A = problem_eval(orc, model, p, dyn, z[:nx], 0.0, 0.0, z)
     Phi = np.stack([A[nx * s:nx * s + nx, nx * s:nx * s + nx] for s in range(S - 1)])
     Gam = np.stack([A[nx * (k // sp):nx * (k // sp) + nx, nx * S + k] for k in range(N)])
     return Phi, Gam
@@ -210,13 +216,21 @@ def configs():
     return [(m, sp, mix) for m in ("single", "double") for sp in SPACINGS for mix in TERMINAL_MIXES]
 
 
-def solve_sample(orc, model, sp, mix, lanes):
+def solve_sample(orc, model, sp, mix, lanes, window_length=None, u_cost_weight=None, u_derivative_cost_weight=None,
+                 terminal_weights=None, seed=None):
     """The sample of one configuration: states x0 [NX, lanes] and the oracle's solutions z [dim, lanes] (Optimization.step
-    from a cold start, default parameters at this spacing and these terminal rows)."""
-    tw = TERMINAL_MIXES[mix]
-    tw = None if tw is None else tw[model]
-    p = params_for(orc, model, sp, tw)
-    x0 = sample_states(model, config_seed(model, sp, mix), lanes)
+    from a cold start, default parameters at this spacing and these terminal rows).  window_length, the two control-cost
+    weights, an explicit list of terminal rows (state order, instead of the mix) and the seed of the states may be given;
+    left out, they are the default parameters', the mix's and config_seed's."""
+    if terminal_weights is None:
+        tw = TERMINAL_MIXES[mix]
+        tw = None if tw is None else tw[model]
+    else:
+        tw = [float(v) for v in terminal_weights]
+    over = {k: v for k, v in (("window_length", window_length), ("u_cost_weight", u_cost_weight),
+                              ("u_derivative_cost_weight", u_derivative_cost_weight)) if v is not None}
+    p = params_for(orc, model, sp, tw, **over)
+    x0 = sample_states(model, config_seed(model, sp, mix) if seed is None else seed, lanes)
     z = np.stack([orc.Optimization(p, model=model).step(x0[:, b], DYN[model], 0.0).z for b in range(lanes)], axis=1)
     return p, tw, x0, z
 

@@ -203,12 +203,13 @@ def targets(nx, set_point):
 
 
 def condensed_ref(orc, p, dyn, z, x0, gbar, set_point=SET_POINT, u_prev=U_PREV, terminal_weights=None, model="single",
-                  lin=np.float64):
-    """(g, du) of the condensed form from the blocks of the oracle's A and its defects at z."""
+                  lin=np.float64, blocks=None):
+    """(g, du) of the condensed form from the blocks of the oracle's A and its defects at z.  blocks: (Phi, Gam) to use
+    instead of the oracle's (tests/helpers/plan_shapes.py perturbs them, or takes the single-precision oracle's)."""
     nx, N, sp, S = fr._shape(orc, model, p)
     nq = nx // 2
     z = np.asarray(z, dtype=np.float64)
-    Phi, Gam = fr.blocks_of(orc, p, dyn, z, model)
+    Phi, Gam = fr.blocks_of(orc, p, dyn, z, model) if blocks is None else blocks
     _, c, _, _ = fr.problem_eval(orc, model, p, dyn, x0, set_point, u_prev, z)
     cs = c[:nx * (S - 1)].reshape(S - 1, nx)
     ci = z[:nx] - np.asarray(x0, dtype=np.float64)

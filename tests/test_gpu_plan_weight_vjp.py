@@ -254,7 +254,9 @@ def test_du_is_the_step_of_one_split_pipeline_iteration(pkg):
     """du at n_rows = N against u_after - u_before of one split-pipeline iteration from the same linearisation point, on a
     handle with max_iterations = 1 and lambda = 0, on the lanes where that iteration took the full step unclamped (one merit
     evaluation, the controls moved, none at the limit).  Warm-started from a converged twin's solution so that the full step
-    is the rule; asserted only where at least 90 % of the lanes qualify.  Tolerance: the fp64 parity tests' 1e-5 on u."""
+    is the rule; asserted only where at least 90 % of the lanes qualify.  Tolerance: the fp64 parity tests' 1e-5 on u.
+    The two are not bitwise alike by construction: the solver wraps c_init and the terminal error with wrap_angles, the weight
+    kernel leaves an angle already in (-pi, pi] as it is (wrap_angles_in_place), half an ulp of 2 pi apart (4.4e-16 here)."""
     model, sp, dtype = "single", 10, torch.float64
     dyn = fr.DYN[model]
     xs = fr.sample_states(model, fr.config_seed(model, sp, "default"), B)
